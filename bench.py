@@ -8,7 +8,10 @@ SupConResNet (fwd+bwd, per-view BatchNorm), SupCon loss, SGD, reservoir update. 
 buffer, weights) are resident in HBM before the timed region.  N>1: one independent stream per rank/GPU (weak
 scaling, no data-path collective; one all_gather/all_reduce of scalars at the end).
 
-Prints ONE JSON line on rank 0 (see the task's bench contract) including
+Prints ONE JSON line on rank 0 (see the task's bench contract).  A plain run does only what the headline needs: set-up, pre-roll and
+--warmup steps, ONE timed region of exactly --steps iterations (ms_per_step = its wall time / --steps), the line.  --dump-outputs DIR
+writes the state the timed steps left behind (model state, replay memory: dump_outputs) as DIR/<name>.npy.  --full adds, as before,
+five repeats of the timed region (median reported) and
   roofline     fp32-MFMA utilisation of the conv implicit-GEMM kernels, from HIP-event timing of every launch
   cpu_baseline the oracle restatement of the same step timed on this box's host cores (rank 0, N=1 only)
   also.aser    the second headline configuration of BASELINE.json's metric (configs[2]: ER + ASER retrieve / update, mem 5000,
@@ -188,9 +191,40 @@ def build_agent(workload, seed, device):
     return params, model, agent, hw, ncls
 
 
+DUMP_IMG_SAMPLE_BYTES = 16 << 20     # memory rows dumped whole (fixed seeded sample); every row also enters buffer_img_row_sum
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(model, agent):
+    """What a caller of the timed path holds after its last step (train_learner returns nothing; it leaves the model and the replay
+    memory updated): every entry of the model's state_dict (weights, BatchNorm running statistics), the memory's labels, a fixed seeded
+    sample of its image rows and one float64 sum per row over all of them.  Integers as float64 (exact), floats as float32."""
+    out = {}
+    for k, v in model.state_dict().items():
+        a = v.detach().cpu().numpy()
+        out["model." + k] = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    img = agent.buffer.buffer_img.detach().cpu().numpy()
+    rows = img.reshape(img.shape[0], -1)
+    n = min(rows.shape[0], max(1, DUMP_IMG_SAMPLE_BYTES // (rows.shape[1] * 4)))
+    pick = np.sort(np.random.default_rng(20240).choice(rows.shape[0], n, replace=False))
+    out["buffer_img_sample"] = img[pick].astype(np.float32)
+    out["buffer_img_sample_rows"] = pick.astype(np.float64)
+    out["buffer_img_row_sum"] = rows.sum(axis=1, dtype=np.float64)
+    out["buffer_label"] = agent.buffer.buffer_label.detach().cpu().numpy().astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES
+    return out
+
+
+def dump_outputs(outputs, path):
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def gpu_leg(args, rank, world, local, workload=None, steps=None, warmup=None):
     from ocl_amd import dist as odist
     from ocl_amd import ops
+    headline = workload is None
     workload = workload or args.workload
     steps = steps or args.steps
     warmup = args.warmup if warmup is None else warmup
@@ -217,8 +251,8 @@ def gpu_leg(args, rank, world, local, workload=None, steps=None, warmup=None):
     # warm-up (the flag's W steps)
     agent.train_learner(xw_d, yw)
     torch.cuda.synchronize()
-    # timed region: EXACTLY `steps` iterations between barrier + synchronize on both sides, `repeats` times back to back; the line
-    # reports the MEDIAN repeat (all of them listed beside it)
+    # timed region: EXACTLY `steps` iterations between barrier + synchronize on both sides, `repeats` times back to back (a plain run:
+    # once); the line reports the MEDIAN repeat (all of them listed beside it)
     env_static = gpu_env_static(local)
     reps = []
     for r in range(max(1, args.repeats)):
@@ -234,13 +268,14 @@ def gpu_leg(args, rank, world, local, workload=None, steps=None, warmup=None):
         per_rank = odist.gather_scalars([t_own], device)[:, 0]
         elapsed = odist.max_over_ranks(elapsed, device)
         reps.append(dict(elapsed=elapsed, per_rank=[float(t) for t in per_rank], env=env))
+    outputs = step_outputs(model, agent) if headline and args.dump_outputs else None   # before anything below trains on
     order = sorted(range(len(reps)), key=lambda i: reps[i]["elapsed"])
     med = reps[order[len(order) // 2]]
     elapsed, per_rank = med["elapsed"], med["per_rank"]
     total_steps = odist.sum_over_ranks(steps, device)
     sclk = [r["env"]["sclk_mhz"] for r in reps if r["env"]["sclk_mhz"] is not None]
     pw = [r["env"]["power_w"] for r in reps if r["env"]["power_w"] is not None]
-    out = dict(elapsed=elapsed, total_steps=total_steps, hw=hw, bs=bs, steps=steps,
+    out = dict(elapsed=elapsed, total_steps=total_steps, hw=hw, bs=bs, steps=steps, outputs=outputs,
                per_rank_images_per_s=[float(steps * bs / t) for t in per_rank],
                repeats_ms_per_step=[r["elapsed"] / steps * 1e3 for r in reps], preroll_ms=preroll_ms, preroll_steps=args.preroll,
                env=dict(env_static, sclk_mhz=(sorted(sclk)[len(sclk) // 2] if sclk else None), sclk_mhz_range=[min(sclk), max(sclk)] if sclk else None,
@@ -250,7 +285,7 @@ def gpu_leg(args, rank, world, local, workload=None, steps=None, warmup=None):
     # ---- roofline leg: HIP events around every kernel launch, on the stream the kernels run on (rank 0) -----------
     # With profiling enabled the engine keeps the weight-gradient kernels on the same stream (no overlap), so each duration is
     # that of the kernel alone; `value` above comes from the overlapped product path.
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         n_prof = min(steps, 20)
         xp, yp = synth_u8(n_prof * bs, hw, ncls, 3)
         xp_d = torch.from_numpy(xp).to(device)
@@ -616,15 +651,24 @@ def main():
     ap.add_argument("--no-also", action="store_true", help="skip the ASER / ER / MIR legs (also.*) of the default SCR run")
     ap.add_argument("--preroll", type=int, default=100,
                     help="real training steps run BEFORE the --warmup steps (reported as preroll_steps / preroll_ms; 0 = none)")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (exactly --steps iterations between barriers) is run this many times back to back; "
-                         "ms_per_step / value are the median repeat, every repeat is listed in ms_per_step_repeats")
+                         "ms_per_step / value are the median repeat, every repeat is listed in ms_per_step_repeats (default: 1, "
+                         "with --full 5)")
     ap.add_argument("--no-accuracy", action="store_true", help="skip the accuracy leg")
     ap.add_argument("--also-steps", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beyond the headline: roofline (+ exposed weight-gradient time), cpu_baseline, also.*, accuracy "
+                         "(each still switched off by its --no-* option) and 5 repeats of the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state their last step left (model state_dict, replay memory labels, a seeded "
+                         "sample of its image rows, per-row sums) as DIR/<name>.npy, float32 / float64, 64 MB at most")
     ap.add_argument("--single-stream", action="store_true",
                     help="keep the weight-gradient kernels on the main stream (OCL_SINGLE_STREAM=1): the configuration the roofline "
                          "leg measures kernels in, and the one profiles/*kernel_stats_single_stream* are taken in")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.single_stream:
         os.environ["OCL_SINGLE_STREAM"] = "1"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -650,7 +694,7 @@ def main():
         res = gpu_leg(args, rank, world, local)
         # the other three 1-GPU configurations of BASELINE.json and the accuracy leg belong to the single-GPU record (the scaling runs
         # time the headline step only)
-        if args.workload == "scr" and not args.no_also and world == 1:
+        if args.workload == "scr" and args.full and not args.no_also and world == 1:
             for wl in ("aser", "er", "mir"):
                 also[wl] = gpu_leg(args, rank, world, local, workload=wl, steps=args.also_steps, warmup=10)
     # weight-gradient time the second stream does not hide: the same timed region in a second process whose engine skips the convolution
@@ -670,7 +714,7 @@ def main():
             exposed = dict(error="%s: %s" % (type(e).__name__, str(e)[:160]))
         res["roofline"]["wgrad"]["exposed"] = exposed
     cpu_line, oracle_handle = None, None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         with contextlib.redirect_stdout(sys.stderr):
             # the CPU legs run on the mask the process started with, not on the GPU-local slice the launch loop was pinned to
             if not args.no_cpu_baseline:
@@ -684,6 +728,8 @@ def main():
                 acc_res, acc_seeds = accuracy_leg(args, rank, world, local)
     if rank != 0:
         return
+    if res["outputs"] is not None:
+        dump_outputs(res["outputs"], args.dump_outputs)
     w = WORKLOADS[args.workload]
     bs = res["bs"]
     value = res["total_steps"] * bs / res["elapsed"]

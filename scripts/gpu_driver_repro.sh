@@ -21,7 +21,7 @@ smi() { echo "--- rocm-smi ($1) $(date +%T.%N)"; rocm-smi --showclocks --showpow
     sleep 0.05
   done ) > gpurun_out/${T}_clock_samples.txt 2>&1 &
 SAMPLER=$!
-Q="--no-cpu-baseline --no-accuracy"
+Q="--full --no-cpu-baseline --no-accuracy"
 run() { echo "### $(date +%T.%N) python bench.py $*" >> $O; python bench.py "$@" 2>gpurun_out/${T}_last.err | python -c "
 import json,sys
 for l in sys.stdin:

@@ -2,7 +2,7 @@
 mkdir -p gpurun_out
 export PYTHONDONTWRITEBYTECODE=1 TMPDIR=/tmp
 T=$1; shift
-Q="--no-cpu-baseline --no-also --no-accuracy --no-roofline --single-stream"
+Q="--full --no-cpu-baseline --no-also --no-accuracy --no-roofline --single-stream"
 i=0
 for e in "$@"; do
   [ "$e" = "-" ] && e=""

@@ -5,7 +5,7 @@ T=${1:-r4d}
 for wl in scr er aser; do timeout 120 python scripts/host_cost_probe.py $wl; done > gpurun_out/${T}_host_cost.txt 2>&1; head -5 gpurun_out/${T}_host_cost.txt
 timeout 200 python -m pytest tests/test_gpu_parity2.py -x -q -k "bit_reproducible or single_run_driver" > gpurun_out/${T}_repro.log 2>&1; echo "reproducibility rc=$?"; tail -4 gpurun_out/${T}_repro.log
 timeout 800 python -m pytest tests -m gpu -x -q > gpurun_out/${T}_suite.log 2>&1; echo "suite rc=$?"; tail -4 gpurun_out/${T}_suite.log
-Q="--no-cpu-baseline --no-accuracy --no-also"
+Q="--full --no-cpu-baseline --no-accuracy --no-also"
 for wl in scr er; do
   timeout 200 python bench.py --workload $wl --steps 200 --warmup 20 --repeats 3 $Q 2>gpurun_out/${T}_err.log | python -c "
 import json,sys

@@ -3,7 +3,7 @@ mkdir -p gpurun_out
 export PYTHONDONTWRITEBYTECODE=1
 T=${1:-r4e}
 OCL_GRAPH=1 timeout 500 python -m pytest tests/test_gpu_steps.py tests/test_gpu_net.py tests/test_gpu_parity2.py -x -q -k "not sharded and not bench_gpus and not free_running" > gpurun_out/${T}_tests_graph.log 2>&1; echo "tests (OCL_GRAPH=1) rc=$?"; tail -3 gpurun_out/${T}_tests_graph.log
-Q="--no-cpu-baseline --no-accuracy --no-also"
+Q="--full --no-cpu-baseline --no-accuracy --no-also"
 FP=$PWD/online-continual-learning_amd/libocl_hip_fp64.so
 line() { python -c "
 import json,sys

@@ -3,7 +3,7 @@ mkdir -p gpurun_out
 export PYTHONDONTWRITEBYTECODE=1
 T=${1:-r4f}
 timeout 300 python -m pytest tests/test_gpu_steps.py tests/test_gpu_parity2.py -x -q -k "data_stream or bit_reproducible or single_run_driver" > gpurun_out/${T}_tests.log 2>&1; echo "tests rc=$?"; tail -3 gpurun_out/${T}_tests.log
-Q="--no-cpu-baseline --no-accuracy --no-also"
+Q="--full --no-cpu-baseline --no-accuracy --no-also"
 FP=$PWD/online-continual-learning_amd/libocl_hip_fp64.so
 line() { python -c "
 import json,sys

@@ -2,7 +2,7 @@
 mkdir -p gpurun_out
 export PYTHONDONTWRITEBYTECODE=1
 T=${1:-r4g}
-Q="--no-cpu-baseline --no-accuracy --no-also"
+Q="--full --no-cpu-baseline --no-accuracy --no-also"
 FP=$PWD/online-continual-learning_amd/libocl_hip_fp64.so
 line() { python -c "
 import json,sys

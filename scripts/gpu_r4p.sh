@@ -19,7 +19,7 @@ print("this process runs on CPU", os.sched_getcpu() if hasattr(os, "sched_getcpu
 print("pinned to", (lambda m: (len(m), m[0], m[-1]) if m else None)(odist.pin_to_gpu_numa(0, 1)))
 PY
 cat gpurun_out/${T}_placement.txt
-Q="--no-cpu-baseline --no-accuracy --no-also"
+Q="--full --no-cpu-baseline --no-accuracy --no-also"
 line() { python -c "
 import json,sys
 for l in sys.stdin:

@@ -3,7 +3,7 @@ mkdir -p gpurun_out
 export PYTHONDONTWRITEBYTECODE=1
 T=${1:-r4t}
 timeout 500 python -m pytest tests/test_gpu_net.py tests/test_gpu_steps.py -x -q > gpurun_out/${T}_tests.log 2>&1; echo "tests rc=$?"; tail -3 gpurun_out/${T}_tests.log
-Q="--no-cpu-baseline --no-accuracy --no-also"
+Q="--full --no-cpu-baseline --no-accuracy --no-also"
 line() { python -c "
 import json,sys
 for l in sys.stdin:

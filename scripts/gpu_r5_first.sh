@@ -27,7 +27,7 @@ for E in "OCL_WGRAD_Q=1" "OCL_WGRAD_Q=1 OCL_BNB_EPI2=1"; do
   env $E timeout 1500 python -m pytest tests/ -m gpu -q --tb=short -p no:cacheprovider -x > gpurun_out/${T}_tests_${tag}.log 2>&1
   echo "pytest [$E] rc=$?  $(tail -1 gpurun_out/${T}_tests_${tag}.log)" | tee -a $O
 done
-Q="--no-cpu-baseline --no-accuracy"
+Q="--full --no-cpu-baseline --no-accuracy"
 for rep in 1 2; do for E in "OCL_NONE=1" "OCL_WGRAD_Q=1" "OCL_WGRAD_Q=1 OCL_BNB_EPI2=1"; do
   echo "### bench [$E] rep $rep" >> $O
   env $E timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 $Q 2>/dev/null | python -c "

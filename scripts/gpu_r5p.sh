@@ -8,7 +8,7 @@ T=${1:-r5q}
 O=gpurun_out/${T}_out.txt; : > $O
 timeout 700 python -m pytest tests/test_gpu_steps.py tests/test_gpu_parity2.py -m gpu -q --tb=short -p no:cacheprovider -k "er_ or _er or merged or free_running or reproducible" > gpurun_out/${T}_tests.log 2>&1; echo "tests rc=$?" >> $O
 for i in 1 2; do
-  timeout 300 python bench.py --workload er --gpus 1 --steps 100 --warmup 10 --no-cpu-baseline --no-accuracy --no-also 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --workload er --gpus 1 --steps 100 --warmup 10 --no-cpu-baseline --no-accuracy --no-also 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('er', d['ms_per_step'], d['ms_per_step_repeats'], d['roofline']['launches_per_step_all'])" >> $O
 done

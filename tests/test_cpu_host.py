@@ -202,54 +202,45 @@ def test_metrics_match_hand_computation():
     assert abs(fwt[0] - np.mean([0.0, 0.1])) < 1e-12
 
 
-def test_reference_driver_with_the_integration_patch_reaches_the_hip_boundary():
-    """INTEGRATION.md §1 applied in memory to the REAL reference (utils/name_match.py, utils/setup_elements.py,
-    experiment/run.py): `multiple_run` (experiment/run.py:17-87) builds its data stream, then model / optimiser / agent through
-    the patched registries -- i.e. this repository's classes -- and stops exactly where the product must stop without an
-    MI355X: at the replay memory's device check (no CPU path).  Runs only where /root/reference exists (the build container)."""
-    import importlib
-    import sys
-    from oracle import ref_import as R
-    if not R.available():
-        pytest.skip("reference tree not present on this machine")
-    if torch.cuda.is_available():
-        pytest.skip("a GPU is visible: the wiring is exercised end to end by tests/test_gpu_parity2.py instead")
+def test_integration_patch_wires_the_registries_and_factories_to_the_engine():
+    """INTEGRATION.md §1, taken from the document itself: its three code blocks are run in namespaces standing for the reference's
+    utils/name_match.py (dictionaries holding the reference's keys), utils/setup_elements.py and experiment/run.py.  Afterwards every
+    hot-path key names this repository's class and nothing else moved; the factories and setup_test_loader are the package's.  The
+    driver's construction sequence (experiment/run.py:38-50: model, optimiser, agent through the patched registry) then builds this
+    repository's agent on an MI355X, and without one stops where the product must stop: at the replay memory's device check (no CPU
+    path)."""
     import ocl_amd
-    saved = {k: sys.modules.get(k) for k in list(sys.modules) if k.split(".")[0] in ("utils", "experiment", "continuum", "agents", "models")}
-    nm = R.activate()
-    try:
-        import torchvision.datasets as tvd
-        rng = np.random.default_rng(0)
-        tvd.SYNTHETIC = lambda name, train: (rng.integers(0, 256, (200 if train else 50, 32, 32, 3), dtype=np.uint8),
-                                             np.repeat(np.arange(10), 20 if train else 5))
-        # ---- the three edits of INTEGRATION.md §1 ----
-        nm.agents.update({k: ocl_amd.name_match.agents[k] for k in ('ER', 'SCR')})
-        nm.retrieve_methods.update({k: ocl_amd.name_match.retrieve_methods[k] for k in ('random', 'MIR', 'ASER', 'match', 'mem_match')})
-        nm.update_methods.update({k: ocl_amd.name_match.update_methods[k] for k in ('random', 'GSS', 'ASER')})
-        import utils.setup_elements as se
-        from ocl_amd.setup_elements import setup_architecture, setup_opt
-        se.setup_architecture, se.setup_opt = setup_architecture, setup_opt
-        import experiment.run as run
-        run = importlib.reload(run)                      # `from utils.setup_elements import ...` re-evaluated after the edit
-        from ocl_amd.data import setup_test_loader
-        run.setup_test_loader = setup_test_loader
-        assert run.agents is nm.agents and run.agents['ER'] is ocl_amd.name_match.agents['ER']
-        assert run.setup_architecture is setup_architecture
-        params = R.default_params(agent="ER", retrieve="random", update="random", data="cifar10", cl_type="nc", num_tasks=5, num_runs=1,
-                                  mem_size=50, online=True, cuda=True, fix_order=True)
-        with R.quiet() as out:
-            with pytest.raises(RuntimeError) as ei:
-                run.multiple_run(params)
-        assert "no CPU path" in str(ei.value) or "MI355X" in str(ei.value)
-        assert "Setting up data stream" in out.getvalue()          # the reference's own driver ran up to the agent construction
-        tb = ei.traceback
-        assert any("experiment/run.py" in str(e.path) for e in tb) and any("online-continual-learning_amd" in str(e.path) for e in tb)
-    finally:
-        import torchvision.datasets as tvd
-        tvd.SYNTHETIC = None
-        for k in [k for k in sys.modules if k.split(".")[0] in ("utils", "experiment", "continuum", "agents", "models")]:
-            del sys.modules[k]
-        sys.modules.update({k: v for k, v in saved.items() if v is not None})
+    from ocl_amd import setup_elements, data
+    from oracle import ref_import as R
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec = doc[doc.index("## 1. What a maintainer of the reference changes"):doc.index("Everything else (`general_main.py` CLI")]
+    blocks = re.findall(r"```python\n(.*?)```", sec, flags=re.S)
+    assert len(blocks) == 3, blocks
+    theirs = object()
+    nm = dict(agents={k: theirs for k in ("ER", "EWC", "AGEM", "CNDPM", "LWF", "ICARL", "GDUMB", "SCR")},
+              retrieve_methods={k: theirs for k in ("MIR", "random", "ASER", "match", "mem_match")},
+              update_methods={k: theirs for k in ("random", "GSS", "ASER")})
+    exec(blocks[0], nm)
+    assert {k for k, v in nm["agents"].items() if v is not theirs} == {"ER", "SCR"}
+    assert all(nm["agents"][k] is ocl_amd.name_match.agents[k] for k in ("ER", "SCR"))
+    assert all(v is not theirs for v in nm["retrieve_methods"].values()) and all(v is not theirs for v in nm["update_methods"].values())
+    assert nm["retrieve_methods"] == dict(ocl_amd.name_match.retrieve_methods) and nm["update_methods"] == dict(ocl_amd.name_match.update_methods)
+    se, run = {}, {}
+    exec(blocks[1], se)
+    exec(blocks[2], run)
+    assert se["setup_architecture"] is setup_elements.setup_architecture and se["setup_opt"] is setup_elements.setup_opt
+    assert run["setup_test_loader"] is data.setup_test_loader
+    params = R.default_params(agent="ER", retrieve="random", update="random", data="cifar10", mem_size=50, cuda=True)
+    model = se["setup_architecture"](params)
+    opt = se["setup_opt"](params.optimizer, model, params.learning_rate, params.weight_decay)
+    if torch.cuda.is_available():
+        agent = nm["agents"][params.agent](model.cuda(), opt, params)
+        assert type(agent) is ocl_amd.name_match.agents["ER"] and agent.buffer.buffer_img.is_cuda
+    else:
+        with pytest.raises(RuntimeError) as ei:
+            nm["agents"][params.agent](model, opt, params)
+        assert "no CPU path" in str(ei.value)
+        assert any("online-continual-learning_amd" in str(e.path) for e in ei.traceback)
 
 
 def test_class_balanced_draw_in_c_equals_the_python_loop():

@@ -263,11 +263,116 @@ int ocl_net_debug_copy(ocl_net* net, int slot, int what, int index, float* dst, 
  * BatchNorm2d backward (train mode) fused with the ReLU mask that follows it: dpre = dz * (zmask > 0) (zmask NULL =
  * no ReLU); dy = gamma*invstd*(dpre - mean(dpre) - xhat*mean(dpre*xhat)); dgamma = sum(dpre*xhat), dbeta = sum(dpre).
  * Tensors are NHWC [groups*m_per_group, c]; mean/invstd are [groups, c]. scratch: groups*2*c accumulator cells of 16 bytes
- * (= groups*4*c doubles, 16-byte aligned): the batch sums are accumulated as integers, independent of the order in which the
- * workgroups finish. */
+ * (= groups*4*c doubles, 16-byte aligned).  The batch sums follow ocl_set_deterministic (fp64 atomics, or fixed-point integers);
+ * no arrival scratch is passed, so the one-pass kernel is never taken here (ocl_test_bn_bwd reaches it). */
 int ocl_bn_bwd_nhwc(const float* dz, const float* zmask, const float* y, const float* mean, const float* invstd,
                     const float* gamma, int64_t m_per_group, int groups, int c, float* dy, float* dgamma,
                     float* dbeta, int accumulate, double* scratch, void* stream);
+
+/* Single-layer test hooks (tests/test_gpu_layers.py, tests/test_cpu_forms.py).  They plan, finalize, pack and launch through the
+ * engine's own functions and add no kernel.  Device scratch (weight packs, plan tables, split-K slabs, arrival counters) is allocated
+ * and freed inside; every call synchronises `stream`.  Accumulator cells ("stats") are the engine's 16-byte cells, laid out
+ * [8 replicas][groups][2][C] with replica stride groups*2*C cells; the caller zeroes them. */
+#define OCL_EPI_STATS 1      /* + per-(group, channel) sum / sum of squares into stats */
+#define OCL_EPI_AFFINE 2     /* out = acc*scale[c] + shift[c] */
+#define OCL_EPI_RES 4        /* out += res */
+#define OCL_EPI_RESMASK 8    /* out += res * (resmask > 0) */
+#define OCL_EPI_RELU 16      /* out = max(out, 0) */
+#define OCL_EPI_ACCUM 32     /* out = out_old + value */
+#define OCL_EPI_BNB 64       /* data gradient feeding a BatchNorm backward: ReLU mask + that BatchNorm's two sums into stats */
+
+/* One convolution layer of Reduced-ResNet18 and the pass it is planned for.  cin = 3: the stem (input tensor NHWC with 4 channels,
+ * the fourth zero).  dir 0: forward (in = x [n,hin,win,cinT], out = y [n,ho,wo,cout]); dir 1: data gradient (in = dy, out = dx).
+ * merge (dir 1, 3x3 stride 2): 1 = the four parity classes as one launch where it plans (the engine's choice), 0 = four launches.
+ * xf / bnb: the LDS reservations of the input transform / the EPI_BNB epilogue (ConvGeomDesc); bnb also makes the data-gradient tiles
+ * follow the groups.  force_*: ConvGeomDesc's overrides (0 = planner). */
+typedef struct {
+    int32_t cin, cout, k, stride, hin, win;
+    int32_t n, groups, dir, merge, xf, bnb;
+    int32_t force_mt, force_nt, force_pipe, force_q4, force_cs, force_cw;
+} ocl_test_conv_desc;
+/* family: 0 conv_t_kernel, 1 conv_q_kernel, 2 conv_s_kernel, 3 conv_w_kernel, 4 conv_wx_kernel.  pipe: 1 three-buffer ring; wres: 1
+ * resident weights (else two buffers); ncls: output classes of the launch; pf: patch prefetch units per thread of the instantiation;
+ * bnb_room: the plan reserved the EPI_BNB table. */
+typedef struct {
+    int32_t family, mt, nt, q4, pipe, wres, ncls, pf, bnb_room, grid_x, grid_y, reserved;
+} ocl_test_conv_form;
+/* The launches of a layer (1, or the 4 parity classes): returns their count (<= cap forms written) or < 0.  Host only. */
+int ocl_test_conv_plan(const ocl_test_conv_desc* desc, ocl_test_conv_form* forms, int cap);
+typedef struct {
+    const float* in;
+    const float* w;          /* OIHW [cout, cin, k, k] (packed here by the engine's pack kernel) */
+    float* out;
+    int32_t flags;           /* OCL_EPI_* */
+    int32_t xf;              /* apply the input transform (needs desc->xf) */
+    const float *scale, *shift, *res, *resmask;
+    void* stats;             /* EPI_STATS / EPI_BNB cells over the output channels */
+    const void* xf_stats;    /* producer's cells over the input channels (filled by its EPI_STATS launch) */
+    const float *xf_gamma, *xf_beta;
+    float *xf_save_mean, *xf_save_invstd, *xf_running_mean, *xf_running_var;
+    int64_t* xf_nbt;
+    const float *bnb_y, *bnb_z, *bnb_mean, *bnb_invstd, *bnb_gamma, *bnb_beta;
+} ocl_test_conv_ops;
+/* Runs every launch of the layer (forms: <= cap written); returns the launch count or < 0. */
+int ocl_test_conv(const ocl_test_conv_desc* desc, const ocl_test_conv_ops* ops, ocl_test_conv_form* forms, int cap, void* stream);
+
+/* Weight gradient of one layer (plan_wgrad's inputs): x [n,hin,win,cinT], dy [n,ho,wo,cout] -> grad OIHW. */
+typedef struct {
+    int32_t cin, cout, k, stride, hin, win, n, xf_groups, wg_target, reserved;
+} ocl_test_wgrad_desc;
+/* q_rgw > 0: the 4x4x1 form; multi: form index inside conv_wgrad_multi_kernel (-1: none); s: pixel splits */
+typedef struct {
+    int32_t mtw, ntw, q_rgw, pf, multi, s, grid_x, grid_y;
+} ocl_test_wgrad_form;
+typedef struct {
+    const float* x;
+    const float* dy;
+    float* grad;             /* multi: every layer's grad inside ONE array, the first layer's first */
+    int32_t xf;              /* x is a raw conv output: apply max(fma(x, scale, shift), 0) of its BatchNorm while staging */
+    int32_t reserved;
+    const float *xf_mean, *xf_invstd, *xf_gamma, *xf_beta;
+} ocl_test_wgrad_ops;
+/* multi 0: per layer launch_wgrad + launch_wgrad_reduce; 1: the layers in one conv_wgrad_multi_kernel launch (all of one form set) +
+ * one launch_wgrad_reduce_multi.  ops may be NULL (plan only, host).  Returns 0 or < 0. */
+int ocl_test_wgrad(const ocl_test_wgrad_desc* descs, const ocl_test_wgrad_ops* ops, int n_layers, int multi, int accumulate,
+                   ocl_test_wgrad_form* forms, void* stream);
+
+/* BatchNorm forward from the cells of the producing conv (launch_bn_fwd): every BnFwdArgs field the engine uses, the second set (_b:
+ * the projection shortcut's BatchNorm, z = relu(bn(y) + bn_b(yb))) included; yb NULL = none, frozen_* NULL = batch statistics. */
+typedef struct {
+    const float* y; float* z; const float* res; const void* stats;
+    const float *gamma, *beta; float *running_mean, *running_var; int64_t* nbt; float *save_mean, *save_invstd;
+    const float *frozen_mean, *frozen_var;
+    const float* yb; const void* stats_b; const float *gamma_b, *beta_b; float *running_mean_b, *running_var_b; int64_t* nbt_b;
+    float *save_mean_b, *save_invstd_b; const float *frozen_mean_b, *frozen_var_b;
+    int64_t m_per_group; int32_t groups, c, relu; float momentum, eps; int32_t reserved;
+} ocl_test_bn_fwd_args;
+int ocl_test_bn_fwd(const ocl_test_bn_fwd_args* a, void* stream);
+/* BatchNorm backward (launch_bn_bwd): nsets 1 or 2, frozen, mask_from_y (needs beta).  one_pass = 1 allocates the arrival counter and
+ * the replicated accumulators so that the one-pass kernel can be chosen.  Returns the path that ran (>= 0) or < 0:
+ * 1000 + 10*U + nsets: bn_bwd_chan_kernel<U, nsets>; 2000 + 10*U + nsets: bn_bwd_fused_kernel<U, nsets>; 3000 + nsets: reduce + apply. */
+typedef struct {
+    const float* dz; const float* z;
+    const float* y[2]; const float* mean[2]; const float* invstd[2]; const float* gamma[2]; const float* beta[2];
+    float* dy[2]; float* dgamma[2]; float* dbeta[2];
+    int64_t m_per_group; int32_t groups, c, nsets, accumulate, frozen, mask_from_y, one_pass, reserved;
+} ocl_test_bn_bwd_args;
+int ocl_test_bn_bwd(const ocl_test_bn_bwd_args* a, void* stream);
+/* Apply half after an EPI_BNB data gradient (launch_bn_apply_e): d = the masked gradient that launch wrote, esums = its cells. */
+int ocl_test_bn_apply_e(const float* d, const float* y, const float* mean, const float* invstd, const float* gamma, const void* esums,
+                        int64_t m_per_group, int groups, int c, float* dy, float* dgamma, float* dbeta, int accumulate, void* stream);
+
+/* Every form the network engine plans for one pass of Reduced-ResNet18 (hw x hw input, nf filters): n images in `groups` BatchNorm
+ * groups, train (forward + data gradients + weight gradients) or eval (forward only; n as the engine plans it, i.e. already rounded).
+ * Made by the function the engine's own plan cache calls.  One entry per launch geometry; returns the entry count (<= cap written). */
+typedef struct {
+    int32_t layer, dir, wg_merged, reserved;   /* conv index in module order; dir 0 fwd, 1 data gradient, 2 weight gradient */
+    ocl_test_conv_desc desc;                   /* dir 0 / 1 */
+    ocl_test_conv_form form;
+    ocl_test_wgrad_desc wdesc;                 /* dir 2 */
+    ocl_test_wgrad_form wform;
+} ocl_test_net_form;
+int ocl_test_net_forms(int hw, int nf, int n, int groups, int train, ocl_test_net_form* out, int cap);
 
 /* Run-to-run reproducibility.  The BatchNorm batch sums (forward statistics, backward reductions) are the only accumulations of a
  * step whose order depends on scheduling.  on = 1: they are accumulated as fixed-point integers (associative): every weight is

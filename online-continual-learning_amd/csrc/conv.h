@@ -15,7 +15,8 @@ constexpr int kStatReps = 8;   // replicas of the BatchNorm statistic accumulato
 // to 2^-40 fixed point and added as INTEGERS (two 64-bit words: the low 32 bits of the fixed-point value and the rest), which is
 // associative: the totals, and everything downstream, are bit-identical from run to run
 // (tests/test_gpu_parity2.py::test_training_steps_are_bit_reproducible).  Resolution 2^-40 (9e-13) absolute per partial sum, range
-// |sum| < 2^47; a non-finite partial sum poisons the cell (reads back as NaN).  Two atomics per sum instead of one: +12 % per step.
+// |sum| < 2^47 for the total and |v| < 7e13 (just under 2^46) for each partial sum; a partial beyond that or a non-finite one poisons
+// the cell (reads back as NaN).  Two atomics per sum instead of one: +12 % per step.
 struct alignas(16) StatCell {
     unsigned long long lo;   // sum of the low 32 bits of the addends' fixed-point values
     long long hi;            // sum of the remaining bits (floor(v * 2^8))
@@ -142,6 +143,7 @@ struct ConvGeomDesc {
 };
 
 int plan_conv(const ConvGeomDesc& g, ConvPlan* p);
+int convt_plan_pf(const ConvPlan& p);   // patch prefetch depth of the conv_t_kernel instantiation launch_conv picks for p
 // the plan's tables as the kernel reads them (host arithmetic only); conv_plan_finalize puts them into device memory and sets
 // p->a.blob -- a plan must be finalized before launch_conv (the engine does it at a plan's first launch)
 void conv_plan_tables(const ConvPlan& p, std::vector<int>* out);
@@ -240,6 +242,7 @@ void wgrad_multi_release(WgradMultiTable* t);
 // wg_target > 0: workgroups the pixel split aims at (default 512: a launch of its own fills the machine)
 int plan_wgrad(int N, int Hin, int Win, int Cin, int Ho, int Wo, int Cout, int ksize, int stride, WgradPlan* p, int xf_groups = 0, int wg_target = 0);
 int launch_wgrad(const WgradPlan& p, hipStream_t s);
+int wgrad_plan_pf(const WgradPlan& p);  // patch prefetch depth of the instantiation launch_wgrad / launch_wgrad_multi pick for p
 // sums the S partials and writes/accumulates the OIHW gradient
 int launch_wgrad_reduce(const WgradPlan& p, float* grad_oihw, int accumulate, hipStream_t s);
 
@@ -369,6 +372,8 @@ struct BnApplyEArgs {
     int G, C, accumulate;
 };
 int launch_bn_apply_e(const BnApplyEArgs& a, hipStream_t s);
+// the path the last launch_bn_bwd took (host): 1000 + 10*U + nsets chan<U, nsets>, 2000 + 10*U + nsets fused<U, nsets>, 3000 + nsets reduce + apply
+int bn_bwd_last_path();
 void bn_bwd_tune(int block_cap, int unroll, int phase);
 void bn_bwd_fused_enable(int on);   // one-pass kernel on/off (-1: OCL_BN_FUSED from the environment, default on)   // micro-benchmark overrides; 0 = default (phase 1 reduce only, 2 apply only)
 
@@ -384,6 +389,11 @@ int launch_relu_bwd(const float* dy, const float* a, float* dx, int64_t n, hipSt
 // out[c] (+)= sum_r m[r][c]
 int launch_colsum(const float* m, int rows, int cols, float* out, int accumulate, hipStream_t s);
 int launch_fill(float* p, int64_t n, float v, hipStream_t s);
+
+// ---- test hooks (layer_api.hip) ----------------------------------------------------------------------------
+ConvShape test_conv_shape(const ocl_test_conv_desc& d);
+void test_conv_form(const ConvPlan& p, ocl_test_conv_form* f);
+void test_wgrad_form(const WgradPlan& p, ocl_test_wgrad_form* f);
 
 int conv_kernels_init();
 int wgrad_kernels_init();   // wgrad.hip; called by conv_kernels_init

@@ -1424,6 +1424,8 @@ static conv_fn_t convt_fn(int MT, int NT, int PF, int res, int cls = 0, int pipe
     return nullptr;
 }
 static int convt_pf_for(int units) { return units <= 1024 ? 4 : 8; }
+// the prefetch depth of the conv_t_kernel instantiation launch_conv picks for a plan (also what the test hooks report)
+int convt_plan_pf(const ConvPlan& p) { return convt_pf_for(p.a.imgs * p.a.PR * p.a.PC * (p.a.KC / 4)); }
 
 // ---- conv_t_kernel layout: fills the tile-dependent fields for (MT channel tiles, NT pixel tiles); returns LDS bytes (0: no fit)
 static size_t convt_layout(const ConvGeomDesc& g, ConvArgs& a, int MT, int NT, bool pipe = false) {
@@ -1724,6 +1726,7 @@ static int plan_conv_t(const ConvGeomDesc& g, ConvPlan* p) {
     if (g.force_MT) MT = g.force_MT;
     if (g.force_NT) NT = g.force_NT;
     if (MT < 1 || MT > 5 || NT < 1 || NT > 2 || MT > nt16) return OCL_ERR_ARG;
+    if (g.ncls > 1 && NT != 1) return OCL_ERR_ARG;   // (a forced NT = 2: conv_t_kernel has output classes with one pixel tile per wave only)
     // staged-weight schedule: the three-buffer ring unless OCL_CONV_PIPE=0 asks for the two-buffer one (plan constant: read once)
     static const bool env_pipe = [] { const char* e = getenv("OCL_CONV_PIPE"); return !(e && atoi(e) == 0); }();
     const bool pipe = g.force_pipe > 0 || (g.force_pipe == 0 && env_pipe);
@@ -2117,7 +2120,7 @@ int launch_conv(const ConvPlan& p, hipStream_t s) {
         OCL_LAUNCH_CHECK();
         return OCL_OK;
     }
-    conv_fn_t fn = convt_fn(p.MT, p.NT, convt_pf_for(p.a.imgs * p.a.PR * p.a.PC * (p.a.KC / 4)), p.a.wres, (p.a.cls_pack & 15) > 1, p.a.pipe,
+    conv_fn_t fn = convt_fn(p.MT, p.NT, convt_plan_pf(p), p.a.wres, (p.a.cls_pack & 15) > 1, p.a.pipe,
                             (p.a.flags & EPI_BNB) ? 1 : 0);
     if (!fn) {
         set_error("launch_conv: no kernel for MT=%d NT=%d", p.MT, p.NT);
@@ -2854,6 +2857,9 @@ static int g_bn_fused = -1;   // -1: environment (OCL_BN_FUSED, default on; 0 = 
 static int g_num_cus = 0;
 void bn_bwd_fused_enable(int on) { g_bn_fused = on; }
 
+static int g_bn_bwd_last_path = 0;   // host: the path of the last launch_bn_bwd (bn_bwd_last_path)
+int bn_bwd_last_path() { return g_bn_bwd_last_path; }
+
 int launch_bn_bwd(const BnBwdArgs& a, hipStream_t s) {
     OCL_REQUIRE(a.nsets == 1 || a.nsets == 2, "bn_bwd: nsets=%d", a.nsets);
     const int C4 = a.C / 4, PT = 256 / C4;
@@ -2867,6 +2873,7 @@ int launch_bn_bwd(const BnBwdArgs& a, hipStream_t s) {
     static const bool bn_chan = [] { const char* e = getenv("OCL_BN_CHAN"); return !(e && e[0] == '0'); }();
     if (bn_chan && g_bn_fused && !a.frozen && g_bn_bwd_phase == 0 && a.G <= 2 && C4 >= 16 && a.m_per_group * a.G <= kBnChanThreads) {
         ProfScope ps(PROF_BN, s);
+        g_bn_bwd_last_path = 1010 + a.nsets;
         if (a.nsets == 2) hipLaunchKernelGGL((bn_bwd_chan_kernel<1, 2>), dim3(C4), dim3(kBnChanThreads), 0, s, a);
         else hipLaunchKernelGGL((bn_bwd_chan_kernel<1, 1>), dim3(C4), dim3(kBnChanThreads), 0, s, a);
         OCL_LAUNCH_CHECK();
@@ -2902,6 +2909,7 @@ int launch_bn_bwd(const BnBwdArgs& a, hipStream_t s) {
             ProfScope ps(PROF_BN, s);
             BnBwdArgs af = a;
             af.err = async_error_word_device();
+            g_bn_bwd_last_path = 2000 + (need <= 3 ? 30 : 60) + 2;
             if (need <= 3) hipLaunchKernelGGL((bn_bwd_fused_kernel<3, 2>), dim3(grid), dim3(kBnFusedThreads), 0, s, af);
             else hipLaunchKernelGGL((bn_bwd_fused_kernel<6, 2>), dim3(grid), dim3(kBnFusedThreads), 0, s, af);
             OCL_LAUNCH_CHECK();
@@ -2911,6 +2919,7 @@ int launch_bn_bwd(const BnBwdArgs& a, hipStream_t s) {
             ProfScope ps(PROF_BN, s);
             BnBwdArgs af = a;
             af.err = async_error_word_device();
+            g_bn_bwd_last_path = 2000 + (need <= 3 ? 30 : need <= 6 ? 60 : 120) + 1;
             if (need <= 3) hipLaunchKernelGGL(bn_bwd_fused_kernel<3>, dim3(grid), dim3(kBnFusedThreads), 0, s, af);
             else if (need <= 6) hipLaunchKernelGGL(bn_bwd_fused_kernel<6>, dim3(grid), dim3(kBnFusedThreads), 0, s, af);
             else hipLaunchKernelGGL(bn_bwd_fused_kernel<12>, dim3(grid), dim3(kBnFusedThreads), 0, s, af);
@@ -2926,6 +2935,7 @@ int launch_bn_bwd(const BnBwdArgs& a, hipStream_t s) {
     const int64_t per_block_pixels = (int64_t)PT * passes;
     const int bx = (int)std::max<int64_t>(1, std::min<int64_t>(std::max(1, cap / a.G), (a.m_per_group + per_block_pixels - 1) / per_block_pixels));
     ProfScope ps(PROF_BN, s);
+    g_bn_bwd_last_path = 3000 + a.nsets;
     const size_t sm1 = (size_t)a.nsets * 2 * PT * a.C * 4;
     if (g_bn_bwd_phase != 2) {
         if (U == 1) hipLaunchKernelGGL(bn_bwd_reduce_kernel<1>, dim3(bx, a.G), dim3(256), sm1, s, a);

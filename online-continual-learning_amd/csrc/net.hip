@@ -53,6 +53,7 @@ struct PlanSet {
     std::vector<int64_t> partial_off;           // per conv: its own slab region (batched reduction), floats
     bool batched_reduce = false;                // every layer's slabs fit the workspace side by side
     std::vector<char> dgrad_bnb;                // per conv: its data-gradient plan follows the BatchNorm groups and has room for the EPI_BNB table
+    std::vector<int> wgrad_target;              // per conv: plan_wgrad's wg_target (> 0: split for the merged launch of the pass)
 };
 
 }  // namespace
@@ -374,31 +375,15 @@ static int build_layout(ocl_net* n) {
 // (+17 us: the epilogue's y / mask loads on 18 MB tensors are exposed once per launch): profiles/r5_switches_netcheck.txt
 static const int64_t kBnbEpi2MaxPix = 160 * 1024;
 
-static int get_plans(ocl_net* n, int N, int groups, PlanSet** out) {
-    auto key = std::make_pair(N, groups);
-    auto it = n->plans.find(key);
-    if (it != n->plans.end()) {
-        *out = &it->second;
-        return OCL_OK;
-    }
-    // OCL_LOG_PLANS=1: one line on stderr per plan set made (host time): what a first-seen batch shape costs a running loop
-    static const bool log_plans = [] { const char* e = getenv("OCL_LOG_PLANS"); return e && e[0] == '1'; }();
-    const auto t_plan0 = std::chrono::steady_clock::now();
-    struct PlanLog {
-        bool on; int N, groups; std::chrono::steady_clock::time_point t0; size_t* count;
-        ~PlanLog() {
-            if (on) fprintf(stderr, "[ocl] plan set %zu made for N=%d groups=%d: %.2f ms host\n", *count, N, groups,
-                            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        }
-    };
-    static size_t n_sets = 0;
-    ++n_sets;
-    PlanLog plog{log_plans, N, groups, t_plan0, &n_sets};
-    PlanSet ps;
+// The plans of one pass: every layer's forward, data-gradient and weight-gradient geometry and the planner's choice for it.  Host only
+// (no device state is touched): get_plans caches its result per (N, groups), ocl_test_net_forms lists it for the planner-coverage test.
+static int make_plan_set(const ocl_net* n, int N, int groups, PlanSet* out) {
+    PlanSet& ps = *out;
     ps.fwd.resize(n->convs.size());
     ps.dgrad.resize(n->convs.size());
     ps.wgrad.resize(n->convs.size());
     ps.dgrad_bnb.assign(n->convs.size(), 0);
+    ps.wgrad_target.assign(n->convs.size(), 0);
     // BatchNorm backward of bn1: its two batch sums in the epilogue of conv2's data gradient (EPI_BNB) + a streaming apply kernel instead
     // of the one-pass kernel with its grid-wide arrival (OCL_BNB_EPI=0: the one-pass kernel).  The replicated arena holds <= 2 groups.
     static const bool env_bnb = [] { const char* e = getenv("OCL_BNB_EPI"); return !(e && e[0] == '0'); }();
@@ -409,7 +394,6 @@ static int get_plans(ocl_net* n, int N, int groups, PlanSet** out) {
         g.xf = c.xf_src >= 0 ? 1 : 0;   // room for the input-transform table (used by train-mode passes only)
         int rc = plan_conv(g, &ps.fwd[i]);
         if (rc != OCL_OK) return rc;
-        n->pack_need_fwd |= PACK_TF;
         if (c.Cin != 3) {
             // stride-2 3x3: the four parity classes as one launch where conv_t_kernel can take them (else four launches)
             const bool merge = true;
@@ -437,7 +421,6 @@ static int get_plans(ocl_net* n, int N, int groups, PlanSet** out) {
                 rc = plan_conv(q, &p);
                 if (rc != OCL_OK) return rc;
                 ps.dgrad[i].push_back(p);
-                n->pack_need_bwd |= PACK_TD;
             }
         }
         // (a pass whose weight gradients leave in one launch -- trunk_backward's `defer` -- splits every layer's pixels less)
@@ -445,7 +428,8 @@ static int get_plans(ocl_net* n, int N, int groups, PlanSet** out) {
         // 0.790 / 0.790 / 0.785 / 0.786 / 0.801 ms -- profiles/r6_wgrad_multi_target.txt; 0 = split as for a launch of its own)
         static const int env_mt = [] { const char* e = getenv("OCL_WGRAD_MULTI_TARGET"); return e ? atoi(e) : 96; }();
         const bool merged = env_mt > 0 && N < kTwoStreamMinBatch && (int64_t)N * n->d.in_h * n->d.in_w < (int64_t)kTwoStreamMinBatch * 1024;
-        rc = plan_wgrad(N, c.Hin, c.Win, c.CinT, c.Ho, c.Wo, c.Cout, c.k, c.stride, &ps.wgrad[i], c.xf_src >= 0 ? groups : 0, merged ? env_mt : 0);
+        ps.wgrad_target[i] = merged ? env_mt : 0;
+        rc = plan_wgrad(N, c.Hin, c.Win, c.CinT, c.Ho, c.Wo, c.Cout, c.k, c.stride, &ps.wgrad[i], c.xf_src >= 0 ? groups : 0, ps.wgrad_target[i]);
         if (rc != OCL_OK) return rc;
         if ((int64_t)ps.wgrad[i].partial_floats > n->partial_floats) {
             set_error("net: wgrad partial workspace too small (%zu > %lld floats)", ps.wgrad[i].partial_floats,
@@ -462,6 +446,35 @@ static int get_plans(ocl_net* n, int N, int groups, PlanSet** out) {
         }
         ps.batched_reduce = off <= n->partial_floats && (int)n->convs.size() <= kMaxReduceLayers;
     }
+    return OCL_OK;
+}
+
+static int get_plans(ocl_net* n, int N, int groups, PlanSet** out) {
+    auto key = std::make_pair(N, groups);
+    auto it = n->plans.find(key);
+    if (it != n->plans.end()) {
+        *out = &it->second;
+        return OCL_OK;
+    }
+    // OCL_LOG_PLANS=1: one line on stderr per plan set made (host time): what a first-seen batch shape costs a running loop
+    static const bool log_plans = [] { const char* e = getenv("OCL_LOG_PLANS"); return e && e[0] == '1'; }();
+    const auto t_plan0 = std::chrono::steady_clock::now();
+    struct PlanLog {
+        bool on; int N, groups; std::chrono::steady_clock::time_point t0; size_t* count;
+        ~PlanLog() {
+            if (on) fprintf(stderr, "[ocl] plan set %zu made for N=%d groups=%d: %.2f ms host\n", *count, N, groups,
+                            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        }
+    };
+    static size_t n_sets = 0;
+    ++n_sets;
+    PlanLog plog{log_plans, N, groups, t_plan0, &n_sets};
+    PlanSet ps;
+    int rc = make_plan_set(n, N, groups, &ps);
+    if (rc != OCL_OK) return rc;
+    n->pack_need_fwd |= PACK_TF;
+    for (auto& d : ps.dgrad)
+        if (!d.empty()) n->pack_need_bwd |= PACK_TD;
     auto res = n->plans.emplace(key, std::move(ps));
     *out = &res.first->second;
     return OCL_OK;
@@ -1544,6 +1557,57 @@ int ocl_net_backward(ocl_net* n, int slot, const float* dout, int accumulate, vo
     }
     n->bsums_clean = false;
     return rc;
+}
+
+int ocl_test_net_forms(int hw, int nf, int N, int groups, int train, ocl_test_net_form* out, int cap) {
+    OCL_REQUIRE(N > 0 && groups > 0 && N % groups == 0 && (train || groups == 1), "test_net_forms: N=%d groups=%d train=%d", N, groups, train);
+    ocl_net_desc d;
+    memset(&d, 0, sizeof(d));
+    d.in_h = d.in_w = hw; d.nf = nf; d.n_classes = 10; d.head = 0; d.max_batch = N; d.n_slots = 1;
+    ocl_net* n = nullptr;
+    int rc = ocl_net_create(&d, &n);
+    if (rc != OCL_OK) return rc;
+    PlanSet ps;
+    rc = make_plan_set(n, N, groups, &ps);
+    int cnt = 0;
+    auto put = [&](int layer, int dir) -> ocl_test_net_form* {
+        ocl_test_net_form* e = cnt < cap && out ? &out[cnt] : nullptr;
+        ++cnt;
+        if (e) {
+            memset(e, 0, sizeof(*e));
+            e->layer = layer; e->dir = dir;
+        }
+        return e;
+    };
+    for (size_t i = 0; rc == OCL_OK && i < n->convs.size(); ++i) {
+        const ConvInfo& c = n->convs[i];
+        ocl_test_conv_desc cd;
+        memset(&cd, 0, sizeof(cd));
+        cd.cin = c.Cin; cd.cout = c.Cout; cd.k = c.k; cd.stride = c.stride; cd.hin = c.Hin; cd.win = c.Win; cd.n = N; cd.groups = groups;
+        cd.xf = c.xf_src >= 0 ? 1 : 0;
+        if (ocl_test_net_form* e = put((int)i, 0)) {
+            e->desc = cd;
+            test_conv_form(ps.fwd[i], &e->form);
+        }
+        if (!train) continue;
+        cd.xf = 0;
+        cd.dir = 1;
+        cd.merge = 1;
+        cd.bnb = ps.dgrad_bnb[i];
+        for (auto& p : ps.dgrad[i])
+            if (ocl_test_net_form* e = put((int)i, 1)) {
+                e->desc = cd;
+                test_conv_form(p, &e->form);
+            }
+        if (ocl_test_net_form* e = put((int)i, 2)) {
+            e->wg_merged = ps.wgrad_target[i] > 0;
+            e->wdesc.cin = c.Cin; e->wdesc.cout = c.Cout; e->wdesc.k = c.k; e->wdesc.stride = c.stride; e->wdesc.hin = c.Hin; e->wdesc.win = c.Win;
+            e->wdesc.n = N; e->wdesc.xf_groups = c.xf_src >= 0 ? groups : 0; e->wdesc.wg_target = ps.wgrad_target[i];
+            test_wgrad_form(ps.wgrad[i], &e->wform);
+        }
+    }
+    ocl_net_destroy(n);
+    return rc == OCL_OK ? cnt : rc;
 }
 
 int ocl_net_debug_stop(ocl_net* n, int stage) {

@@ -473,6 +473,8 @@ static wgrad_fn_t wgrad_trace_fn(int M, int N, int PF, int rgw) {
     return nullptr;
 }
 static int wgrad_pf_for(int units) { return units <= 1024 ? 4 : 8; }
+// the prefetch depth of the instantiation launch_wgrad / launch_wgrad_multi pick for a plan (also what the test hooks report)
+int wgrad_plan_pf(const WgradPlan& p) { return wgrad_pf_for(p.a.imgs * p.a.PR * p.a.PC * (p.a.KC / 4)); }
 
 // sums the split-K partials into the OIHW gradient: grad[co][ci][t] (+)= sum_s partial[s][(chunk,t,cc)][co].
 // 32 consecutive outputs (co fastest: coalesced partial reads) x 8 split lanes per block; the 8 lane sums are combined
@@ -725,7 +727,7 @@ int plan_wgrad(int N, int Hin, int Win, int Cin, int Ho, int Wo, int Cout, int k
 }
 
 int launch_wgrad(const WgradPlan& p, hipStream_t s) {
-    const int pf = wgrad_pf_for(p.a.imgs * p.a.PR * p.a.PC * (p.a.KC / 4));
+    const int pf = wgrad_plan_pf(p);
     wgrad_fn_t fn = p.q_rgw ? wgrad_q_fn(p.q_rgw, pf) : wgrad_fn(p.MTW, p.NTW, pf);
     if (p.a.trace) {
         fn = wgrad_trace_fn(p.MTW, p.NTW, pf, p.q_rgw);
@@ -747,7 +749,7 @@ int launch_wgrad(const WgradPlan& p, hipStream_t s) {
 
 int wgrad_multi_variant(const WgradPlan& p) {
     if (p.q_rgw || p.a.trace) return -1;
-    const int pf = wgrad_pf_for(p.a.imgs * p.a.PR * p.a.PC * (p.a.KC / 4));
+    const int pf = wgrad_plan_pf(p);
     if (p.MTW == 1 && p.NTW == 2) return pf == 4 ? 0 : 1;
     if (p.MTW == 1 && p.NTW == 3) return pf == 4 ? 2 : 3;
     if (p.MTW == 2 && p.NTW == 3 && pf == 8) return 4;

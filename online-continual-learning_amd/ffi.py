@@ -25,6 +25,58 @@ class NetDesc(C.Structure):
                 ("feat_dim", i32), ("max_batch", i32), ("n_slots", i32)]
 
 
+
+# single-layer test hooks (ocl_test_*: tests/test_gpu_layers.py, tests/test_cpu_forms.py)
+def _ints(*names):
+    return [(n, i32) for n in names]
+
+
+class TestConvDesc(C.Structure):
+    _fields_ = _ints("cin", "cout", "k", "stride", "hin", "win", "n", "groups", "dir", "merge", "xf", "bnb",
+                     "force_mt", "force_nt", "force_pipe", "force_q4", "force_cs", "force_cw")
+
+
+class TestConvForm(C.Structure):
+    _fields_ = _ints("family", "mt", "nt", "q4", "pipe", "wres", "ncls", "pf", "bnb_room", "grid_x", "grid_y", "reserved")
+
+
+class TestConvOps(C.Structure):
+    _fields_ = [("in_", vp), ("w", vp), ("out", vp), ("flags", i32), ("xf", i32), ("scale", vp), ("shift", vp), ("res", vp),
+                ("resmask", vp), ("stats", vp), ("xf_stats", vp), ("xf_gamma", vp), ("xf_beta", vp), ("xf_save_mean", vp),
+                ("xf_save_invstd", vp), ("xf_running_mean", vp), ("xf_running_var", vp), ("xf_nbt", vp), ("bnb_y", vp), ("bnb_z", vp),
+                ("bnb_mean", vp), ("bnb_invstd", vp), ("bnb_gamma", vp), ("bnb_beta", vp)]
+
+
+class TestWgradDesc(C.Structure):
+    _fields_ = _ints("cin", "cout", "k", "stride", "hin", "win", "n", "xf_groups", "wg_target", "reserved")
+
+
+class TestWgradForm(C.Structure):
+    _fields_ = _ints("mtw", "ntw", "q_rgw", "pf", "multi", "s", "grid_x", "grid_y")
+
+
+class TestWgradOps(C.Structure):
+    _fields_ = [("x", vp), ("dy", vp), ("grad", vp), ("xf", i32), ("reserved", i32), ("xf_mean", vp), ("xf_invstd", vp),
+                ("xf_gamma", vp), ("xf_beta", vp)]
+
+
+class TestBnFwdArgs(C.Structure):
+    _fields_ = [(n, vp) for n in ("y", "z", "res", "stats", "gamma", "beta", "running_mean", "running_var", "nbt", "save_mean",
+                                  "save_invstd", "frozen_mean", "frozen_var", "yb", "stats_b", "gamma_b", "beta_b", "running_mean_b",
+                                  "running_var_b", "nbt_b", "save_mean_b", "save_invstd_b", "frozen_mean_b", "frozen_var_b")] + \
+              [("m_per_group", i64), ("groups", i32), ("c", i32), ("relu", i32), ("momentum", f32), ("eps", f32), ("reserved", i32)]
+
+
+class TestBnBwdArgs(C.Structure):
+    _fields_ = [("dz", vp), ("z", vp)] + [(n, vp * 2) for n in ("y", "mean", "invstd", "gamma", "beta", "dy", "dgamma", "dbeta")] + \
+              [("m_per_group", i64)] + _ints("groups", "c", "nsets", "accumulate", "frozen", "mask_from_y", "one_pass", "reserved")
+
+
+class TestNetForm(C.Structure):
+    _fields_ = _ints("layer", "dir", "wg_merged", "reserved") + [("desc", TestConvDesc), ("form", TestConvForm),
+                                                                   ("wdesc", TestWgradDesc), ("wform", TestWgradForm)]
+
+
 # name -> (restype, argtypes); kept in one table so tests can check it against the header
 SIGNATURES = {
     "ocl_version": (C.c_int, []),
@@ -74,6 +126,13 @@ SIGNATURES = {
     "ocl_net_debug_copy": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, i64, C.POINTER(i64), vp]),
     "ocl_bn_bwd_nhwc": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]),
     "ocl_set_deterministic": (C.c_int, [C.c_int]),
+    "ocl_test_conv_plan": (C.c_int, [C.POINTER(TestConvDesc), C.POINTER(TestConvForm), C.c_int]),
+    "ocl_test_conv": (C.c_int, [C.POINTER(TestConvDesc), C.POINTER(TestConvOps), C.POINTER(TestConvForm), C.c_int, vp]),
+    "ocl_test_wgrad": (C.c_int, [C.POINTER(TestWgradDesc), C.POINTER(TestWgradOps), C.c_int, C.c_int, C.c_int, C.POINTER(TestWgradForm), vp]),
+    "ocl_test_bn_fwd": (C.c_int, [C.POINTER(TestBnFwdArgs), vp]),
+    "ocl_test_bn_bwd": (C.c_int, [C.POINTER(TestBnBwdArgs), vp]),
+    "ocl_test_bn_apply_e": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
+    "ocl_test_net_forms": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TestNetForm), C.c_int]),
     "ocl_prof_enable": (C.c_int, [C.c_int]),
     "ocl_prof_reset": (C.c_int, []),
     "ocl_prof_query": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(i64)]),

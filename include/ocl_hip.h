@@ -96,7 +96,9 @@ int ocl_kd_fwd_bwd(const float* scores, const float* target_scores, int n, int c
  * SupConLoss.forward with contrast_mode='all' (utils/loss.py:19-96).  feat is VIEW-MAJOR
  * [n_views*bsz, dim] (= torch.cat(torch.unbind(features,1)), loss.py:56).  workspace: at least
  * ocl_supcon_workspace_bytes(bsz*n_views).  dfeat may be NULL (loss only). An anchor without any
- * positive yields NaN exactly as the reference's 0/0 (loss.py:90). */
+ * positive (n_views = 1 and a label that occurs once) yields what the reference's 0/0 yields (loss.py:90) under autograd: a NaN
+ * loss AND a NaN in every element of dfeat (the 1/0 of that anchor's mean meets the zero mask, 0 * inf, in every logit of its
+ * row, and every feature row takes part in that row's logits). */
 int64_t ocl_supcon_workspace_bytes(int n_anchor);
 int ocl_supcon_fwd_bwd(const float* feat, const int64_t* y, int bsz, int n_views, int dim,
                        float temperature, float* loss_out, float* dfeat, void* workspace,
@@ -120,7 +122,8 @@ int ocl_col_reduce(const float* m, int rows, int cols, int mode, float* out, voi
 int ocl_aser_score(const float* sv_adv, int n_adv, const float* sv_coop, int n_coop, int n_cand,
                    int type, float* out, void* stream);
 /* sv.argsort(descending=True) (aser_retrieve.py:88, aser_update.py:88; scores.sort(descending)
- * mir_retrieve.py:29).  Deterministic: ties keep ascending index. n <= OCL_SORT_MAX. */
+ * mir_retrieve.py:29).  Deterministic: ties keep ascending index (-0.0 and +0.0 are a tie).  NaN sorts first, before +inf, in
+ * index order among NaNs: torch.argsort(descending=True, stable=True).  n <= OCL_SORT_MAX. */
 #define OCL_SORT_MAX 4096
 int ocl_argsort_desc(const float* v, int n, int64_t* idx_out, void* stream);
 
@@ -373,6 +376,87 @@ typedef struct {
     ocl_test_wgrad_form wform;
 } ocl_test_net_form;
 int ocl_test_net_forms(int hw, int nf, int n, int groups, int train, ocl_test_net_form* out, int cap);
+
+/* ---- which path a small-op entry point takes (tests) ------------------------------------------------
+ * Host-only (no launch, no GPU): the kernel variant, grid and LDS size that the entry points of csrc/small_ops.hip choose for the
+ * given sizes and pointer VALUES (only their alignment is looked at; nothing is dereferenced).  The entry points call the same
+ * functions to launch, so the answer cannot drift from what runs.  tests/test_cpu_small_ops.py requires a parity case in
+ * tests/small_op_cases.py for every OCL_PATH_* below.  args (int64 each), by op:
+ *   ROWS        src, dst, row_bytes, n                  (ocl_gather_rows / ocl_scatter_rows)
+ *   PAIR        src_a, dst_a, row_bytes_a, row_bytes_b, n
+ *   U8          n, h, w, c
+ *   SGD         params, grads, out, n
+ *   COSINE      mem, g, k, n
+ *   CE          n, c, reduction      CE_SEG / KD / MIR: n, c
+ *   SUPCON      feat, bsz, n_views, dim, want_grad
+ *   KNN         cand_f, n_eval, n_cand, dim, k
+ *   COL_REDUCE  rows, cols           ASER: n_cand
+ *   ARGSORT     n
+ *   NCM_MEANS   d, n_cls             NCM_PREDICT: n, d, n_cls
+ *   GEMM        m, n, k
+ * Returns the OCL_PATH_* code (> 0) and fills *plan (may be NULL); 0 for an unknown op or a wrong argument count.  A *_REFUSED code
+ * means the entry point returns OCL_ERR_ARG on the host before any launch. */
+enum {
+    OCL_SOP_ROWS = 0, OCL_SOP_PAIR = 1, OCL_SOP_U8 = 2, OCL_SOP_SGD = 3, OCL_SOP_COSINE = 4, OCL_SOP_CE = 5, OCL_SOP_CE_SEG = 6,
+    OCL_SOP_KD = 7, OCL_SOP_MIR = 8, OCL_SOP_SUPCON = 9, OCL_SOP_KNN = 10, OCL_SOP_COL_REDUCE = 11, OCL_SOP_ASER = 12,
+    OCL_SOP_ARGSORT = 13, OCL_SOP_NCM_MEANS = 14, OCL_SOP_NCM_PREDICT = 15, OCL_SOP_GEMM = 16
+};
+enum {
+    OCL_PATH_ROWS_COPY16 = 1,          /* 16-byte units (row_bytes % 16 == 0, src and dst 16-byte aligned), grid.y < 8 */
+    OCL_PATH_ROWS_COPY16_YCAP = 2,     /* ... grid.y at its cap of 8 (rows > 112 KB) */
+    OCL_PATH_ROWS_COPY4 = 3,           /* 4-byte units */
+    OCL_PATH_ROWS_COPY4_YCAP = 4,      /* ... grid.y = 8 (rows > 28 KB) */
+    OCL_PATH_PAIR_FUSED = 5,           /* one rows_gather_pair launch, b's row in one trip (<= 256 units of 4 bytes) */
+    OCL_PATH_PAIR_FUSED_BLOOP = 6,     /* ... b's row takes several trips */
+    OCL_PATH_PAIR_FALLBACK = 7,        /* a not 16-byte copyable: two rows_copy launches */
+    OCL_PATH_U8_GATHER = 8,
+    OCL_PATH_SGD_VEC = 9,              /* n % 4 == 0 */
+    OCL_PATH_SGD_TAIL = 10,            /* scalar tail of 1 - 3 elements */
+    OCL_PATH_SGD_GRID_CAP = 11,        /* 2048 workgroups: the grid-stride loop takes more than one trip */
+    OCL_PATH_SGD_REFUSED = 12,         /* a pointer that is not 16-byte aligned */
+    OCL_PATH_COS_VEC_ONE = 13,         /* float4 loads; one workgroup */
+    OCL_PATH_COS_VEC_MULTI = 14,
+    OCL_PATH_COS_VEC_CAP = 15,         /* 512 workgroups */
+    OCL_PATH_COS_SCALAR_ONE = 16,      /* n % 4 != 0, or mem / g not 16-byte aligned */
+    OCL_PATH_COS_SCALAR_MULTI = 17,
+    OCL_PATH_COS_SCALAR_CAP = 18,
+    OCL_PATH_CE_NONE = 19,
+    OCL_PATH_CE_MEAN = 20,
+    OCL_PATH_CE_SEG = 21,
+    OCL_PATH_KD = 22,
+    OCL_PATH_MIR = 23,
+    OCL_PATH_SUPCON_VEC_TAIL = 24,     /* supcon_rows: 16-byte dot product (dim % 4 == 0, feat aligned); supcon_grad: A % 16 != 0 */
+    OCL_PATH_SUPCON_VEC_NOTAIL = 25,
+    OCL_PATH_SUPCON_VEC_LOSS = 26,     /* dfeat == NULL: supcon_grad is one workgroup that reduces the loss */
+    OCL_PATH_SUPCON_SCALAR_TAIL = 27,
+    OCL_PATH_SUPCON_SCALAR_NOTAIL = 28,
+    OCL_PATH_SUPCON_SCALAR_LOSS = 29,
+    OCL_PATH_SUPCON_REFUSED = 30,      /* A > 8192 or dim > 4096 */
+    OCL_PATH_KNN_VEC_UNROLL = 31,      /* one thread per candidate, 16-byte loads: dim / 4 a multiple of 4 (unrolled loop only) */
+    OCL_PATH_KNN_VEC_REM = 32,         /* dim / 4 < 4 (remainder loop only) */
+    OCL_PATH_KNN_VEC_BOTH = 33,        /* both loops in one row */
+    OCL_PATH_KNN_WAVE = 34,            /* dim % 4 != 0 or cand_f misaligned: one wave per candidate */
+    OCL_PATH_KNN_REFUSED = 35,         /* n_cand > OCL_KNN_MAX_CAND */
+    OCL_PATH_COL_REDUCE = 36,
+    OCL_PATH_ASER_SCORE = 37,
+    OCL_PATH_ARGSORT_FULL = 38,        /* n a power of two: no padding entries */
+    OCL_PATH_ARGSORT_PADDED = 39,
+    OCL_PATH_ARGSORT_REFUSED = 40,     /* n > OCL_SORT_MAX */
+    OCL_PATH_NCM_MEANS = 41,
+    OCL_PATH_NCM_PREDICT = 42,
+    OCL_PATH_GEMM_K16 = 43,            /* k % 16 == 0: the unrolled loop only */
+    OCL_PATH_GEMM_KTAIL = 44,          /* k < 16: the 4-wide tail loop only */
+    OCL_PATH_GEMM_KBOTH = 45
+};
+typedef struct {
+    int32_t path;                      /* OCL_PATH_* */
+    int32_t aux;                       /* cosine: workgroups; knn / argsort: the padded power of two; otherwise 0 */
+    uint32_t grid_x, grid_y, block;    /* first (or only) launch; all 0 for a refusal */
+    uint32_t grid2_x, block2;          /* second launch (cosine finish, supcon_grad, the pair fallback's b copy); 0 if none */
+    uint32_t reserved;
+    int64_t lds_bytes, lds2_bytes;     /* dynamic LDS of the two launches */
+} ocl_small_op_plan;
+int ocl_test_small_op_path(int op, const int64_t* args, int n_args, ocl_small_op_plan* plan);
 
 /* Run-to-run reproducibility.  The BatchNorm batch sums (forward statistics, backward reductions) are the only accumulations of a
  * step whose order depends on scheduling.  on = 1: they are accumulated as fixed-point integers (associative): every weight is

@@ -7,6 +7,106 @@
 using namespace ocl;
 
 // =====================================================================================================
+// Launch plans: which kernel variant, grid and LDS size an entry point takes for given sizes and pointer alignments.  Host-only;
+// the entry points below launch from these, and ocl_test_small_op_path reports them (tests/test_cpu_small_ops.py).
+// =====================================================================================================
+typedef ocl_small_op_plan SPlan;
+static SPlan splan(int path, unsigned gx = 0, unsigned gy = 0, unsigned block = 0, int64_t lds = 0) {
+    SPlan p = {};
+    p.path = path;
+    p.grid_x = gx; p.grid_y = gy; p.block = block; p.lds_bytes = lds;
+    return p;
+}
+static int next_pow2(int v) {
+    int p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) % 16) == 0;
+}
+static unsigned rows_grid_y(int64_t units) { return (unsigned)max((int64_t)1, min((int64_t)8, (units + 1023) / 1024)); }
+
+static SPlan plan_rows(const void* src, const void* dst, int64_t row_bytes, int64_t n) {
+    const bool v16 = (row_bytes % 16) == 0 && aligned16(src, dst);
+    const unsigned gy = rows_grid_y(row_bytes / (v16 ? 16 : 4));
+    const int path = v16 ? (gy == 8 ? OCL_PATH_ROWS_COPY16_YCAP : OCL_PATH_ROWS_COPY16) : (gy == 8 ? OCL_PATH_ROWS_COPY4_YCAP : OCL_PATH_ROWS_COPY4);
+    return splan(path, (unsigned)n, gy, 256);
+}
+static SPlan plan_pair(const void* src_a, const void* dst_a, int64_t row_bytes_a, int64_t row_bytes_b, int64_t n) {
+    const bool v16 = (row_bytes_a % 16) == 0 && aligned16(src_a, dst_a);
+    if (!v16) {   // two rows_copy launches (each planned by plan_rows from its own pointers)
+        SPlan p = splan(OCL_PATH_PAIR_FALLBACK, (unsigned)n, rows_grid_y(row_bytes_a / 4), 256);
+        p.grid2_x = (unsigned)n; p.block2 = 256;
+        return p;
+    }
+    return splan(row_bytes_b / 4 > 256 ? OCL_PATH_PAIR_FUSED_BLOOP : OCL_PATH_PAIR_FUSED, (unsigned)n, rows_grid_y(row_bytes_a / 16), 256);
+}
+static SPlan plan_u8(int64_t n, int h, int w, int c) {
+    const int64_t per = (int64_t)h * w * c;
+    return splan(OCL_PATH_U8_GATHER, (unsigned)n, (unsigned)max((int64_t)1, min((int64_t)16, (per + 2047) / 2048)), 256);
+}
+static SPlan plan_sgd(const void* params, const void* grads, const void* out, int64_t n) {
+    if (!aligned16(params, grads, out)) return splan(OCL_PATH_SGD_REFUSED);
+    const int blocks = (int)min((int64_t)2048, (n / 4 + 255) / 256 + 1);
+    const bool more_trips = n / 4 > (int64_t)blocks * 256;
+    return splan(more_trips ? OCL_PATH_SGD_GRID_CAP : (n % 4) ? OCL_PATH_SGD_TAIL : OCL_PATH_SGD_VEC, (unsigned)blocks, 1, 256);
+}
+constexpr int kCosChunk = 4;   // float4 per thread and pass
+constexpr int kCosMaxBlocks = 512;
+// (the size and form variants of a path are consecutive codes: plan_cosine and plan_supcon add an offset to the first)
+static_assert(OCL_PATH_COS_VEC_CAP == OCL_PATH_COS_VEC_ONE + 2 && OCL_PATH_COS_VEC_MULTI == OCL_PATH_COS_VEC_ONE + 1 &&
+              OCL_PATH_COS_SCALAR_CAP == OCL_PATH_COS_SCALAR_ONE + 2 && OCL_PATH_COS_SCALAR_MULTI == OCL_PATH_COS_SCALAR_ONE + 1, "cosine path codes");
+static_assert(OCL_PATH_SUPCON_VEC_NOTAIL == OCL_PATH_SUPCON_VEC_TAIL + 1 && OCL_PATH_SUPCON_VEC_LOSS == OCL_PATH_SUPCON_VEC_TAIL + 2 &&
+              OCL_PATH_SUPCON_SCALAR_NOTAIL == OCL_PATH_SUPCON_SCALAR_TAIL + 1 && OCL_PATH_SUPCON_SCALAR_LOSS == OCL_PATH_SUPCON_SCALAR_TAIL + 2, "supcon path codes");
+static SPlan plan_cosine(const void* mem, const void* g, int k, int64_t n) {
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(kCosMaxBlocks, (n / 4 + 256 * kCosChunk - 1) / (256 * kCosChunk)));
+    const bool vec = n % 4 == 0 && aligned16(mem, g);   // rows are 16-byte aligned -> float4 loads; otherwise scalar loads (any n)
+    const int size = blocks == 1 ? 0 : blocks == kCosMaxBlocks ? 2 : 1;
+    SPlan p = splan((vec ? OCL_PATH_COS_VEC_ONE : OCL_PATH_COS_SCALAR_ONE) + size, (unsigned)blocks, 1, 256);
+    p.aux = blocks;
+    p.grid2_x = 1; p.block2 = 64;
+    return p;
+}
+// the in-kernel predicate of supcon_rows' 16-byte dot product (plan_supcon answers from the same expression)
+__host__ __device__ __forceinline__ bool supcon_vec(const float* feat, int dim) { return (dim & 3) == 0 && (((uintptr_t)feat) & 15) == 0; }
+static SPlan plan_supcon(const float* feat, int bsz, int n_views, int dim, bool want_grad) {
+    const int64_t A = (int64_t)bsz * n_views;
+    if (A > 8192 || dim > 4096) return splan(OCL_PATH_SUPCON_REFUSED);
+    const int form = !want_grad ? 2 : (A % 16) ? 0 : 1;
+    SPlan p = splan((supcon_vec(feat, dim) ? OCL_PATH_SUPCON_VEC_TAIL : OCL_PATH_SUPCON_SCALAR_TAIL) + form, (unsigned)A, 1, 256,
+                    (int64_t)(dim + A + 16) * (int64_t)sizeof(float));
+    p.grid2_x = want_grad ? (unsigned)A : 1u; p.block2 = 128;
+    p.lds2_bytes = (int64_t)std::max<int64_t>(A, 128) * (int64_t)sizeof(float);
+    return p;
+}
+// the in-kernel predicate of knn_sv_kernel's one-thread-per-candidate distance loop
+__host__ __device__ __forceinline__ bool knn_vec(const float* cand_f, int dim) { return (dim & 3) == 0 && (((uintptr_t)cand_f) & 15) == 0; }
+static SPlan plan_knn(const float* cand_f, int n_eval, int n_cand, int dim) {
+    if (n_cand > OCL_KNN_MAX_CAND) return splan(OCL_PATH_KNN_REFUSED);
+    const int P = next_pow2(n_cand), d4n = dim >> 2;
+    const int path = !knn_vec(cand_f, dim) ? OCL_PATH_KNN_WAVE : d4n < 4 ? OCL_PATH_KNN_VEC_REM : (d4n % 4) ? OCL_PATH_KNN_VEC_BOTH : OCL_PATH_KNN_VEC_UNROLL;
+    SPlan p = splan(path, (unsigned)n_eval, 1, 256, (int64_t)P * (8 + 4 + 4) + (int64_t)dim * 4);
+    p.aux = P;
+    return p;
+}
+static SPlan plan_argsort(int n) {
+    if (n > OCL_SORT_MAX) return splan(OCL_PATH_ARGSORT_REFUSED);
+    const int P = next_pow2(n);
+    SPlan p = splan(P == n ? OCL_PATH_ARGSORT_FULL : OCL_PATH_ARGSORT_PADDED, 1, 1, 256, (int64_t)P * 8);
+    p.aux = P;
+    return p;
+}
+static SPlan plan_ce(int path) { return splan(path, 1, 1, 256); }   // ce / ce_seg / kd: a single workgroup, one wave per row
+static SPlan plan_mir(int n) { return splan(OCL_PATH_MIR, (unsigned)cdiv(n, 4), 1, 256); }
+static SPlan plan_cols(int path, int cols) { return splan(path, (unsigned)cdiv(cols, 32), 1, 256); }
+static SPlan plan_ncm_means(int d, int n_cls) { return splan(OCL_PATH_NCM_MEANS, (unsigned)n_cls, 1, 256, (int64_t)d * 8 + 64); }
+static SPlan plan_ncm_predict(int n, int d, int n_cls) { return splan(OCL_PATH_NCM_PREDICT, (unsigned)n, 1, 256, (int64_t)(d + n_cls + 16) * 4); }
+static SPlan plan_gemm(int m, int n, int k) {
+    return splan(k % 16 == 0 ? OCL_PATH_GEMM_K16 : k < 16 ? OCL_PATH_GEMM_KTAIL : OCL_PATH_GEMM_KBOTH, (unsigned)cdiv(n, 16), (unsigned)cdiv(m, 16), 64);
+}
+
+// =====================================================================================================
 // K9 gather / scatter of replay-buffer rows
 // =====================================================================================================
 template <bool SCATTER>
@@ -38,16 +138,12 @@ static int rows_copy(const void* src, const int64_t* idx, int64_t n, int64_t row
     OCL_REQUIRE(src && idx && dst, "rows_copy: null pointer");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_KNN, s);
-    const bool v16 = (row_bytes % 16) == 0 && (((uintptr_t)src | (uintptr_t)dst) % 16) == 0;
-    if (v16) {
-        const int64_t units = row_bytes / 16;
-        dim3 grid((unsigned)n, (unsigned)max((int64_t)1, min((int64_t)8, (units + 1023) / 1024)));
-        hipLaunchKernelGGL(rows_copy16<SCATTER>, grid, dim3(256), 0, s, (const uint4*)src, idx, (uint4*)dst, units);
-    } else {
-        const int64_t units = row_bytes / 4;
-        dim3 grid((unsigned)n, (unsigned)max((int64_t)1, min((int64_t)8, (units + 1023) / 1024)));
-        hipLaunchKernelGGL(rows_copy4<SCATTER>, grid, dim3(256), 0, s, (const uint32_t*)src, idx, (uint32_t*)dst, units);
-    }
+    const SPlan pl = plan_rows(src, dst, row_bytes, n);
+    const dim3 grid(pl.grid_x, pl.grid_y);
+    if (pl.path == OCL_PATH_ROWS_COPY16 || pl.path == OCL_PATH_ROWS_COPY16_YCAP)
+        hipLaunchKernelGGL(rows_copy16<SCATTER>, grid, dim3(pl.block), 0, s, (const uint4*)src, idx, (uint4*)dst, row_bytes / 16);
+    else
+        hipLaunchKernelGGL(rows_copy4<SCATTER>, grid, dim3(pl.block), 0, s, (const uint32_t*)src, idx, (uint32_t*)dst, row_bytes / 4);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -109,7 +205,7 @@ __global__ void __launch_bounds__(256) sgd_flat(float* __restrict__ p, const flo
 // it; fp32 lane partials, fp64 from the wave reduction on, one fp64 partial per (workgroup, row) in the workspace
 // [blocks][2k + 1] -- no atomics: pass 2 (one wave) sums the workgroups' partials in a fixed order, so the scores (which feed hard
 // decisions: `batch_sim < 0`, multinomial weights, the stored buffer_score) are bit-reproducible run to run.
-constexpr int kCosChunk = 4;   // float4 per thread and pass
+// (kCosChunk float4 per thread and pass size the grid: plan_cosine)
 // VEC: rows are 16-byte aligned (n % 4 == 0) -> float4 loads; otherwise scalar loads (any n)
 template <bool VEC>
 __global__ void __launch_bounds__(256) cosine_partial_kernel(const float* __restrict__ mem, int k, int64_t n,
@@ -174,8 +270,10 @@ __global__ void __launch_bounds__(64) cosine_finish_kernel(const double* __restr
 // =====================================================================================================
 // K6 cross-entropy: single workgroup, one wave per row, deterministic mean
 // =====================================================================================================
+// exact (optional): the row loss with its three pieces (log of the sum, the max, the label's logit) combined in double, for a caller
+// that subtracts two row losses (mir_kernel: the difference is small against the losses, whose fp32 roundings would dominate it)
 __device__ __forceinline__ float ce_row(const float* __restrict__ x, int c, int64_t y, int lane, float* __restrict__ dx,
-                                        float scale) {
+                                        float scale, double* exact = nullptr) {
     float m = -INFINITY;
     for (int j = lane; j < c; j += 64) m = fmaxf(m, x[j]);
     m = wave_max(m);
@@ -191,6 +289,7 @@ __device__ __forceinline__ float ce_row(const float* __restrict__ x, int c, int6
             dx[j] = (p - (j == (int)y ? 1.f : 0.f)) * scale;
         }
     }
+    if (exact) *exact = ((double)logf(s) + (double)m) - (double)xy;
     return lse - xy;
 }
 
@@ -260,31 +359,32 @@ __global__ void __launch_bounds__(256) kd_kernel(const float* __restrict__ score
                                                  float T, float* __restrict__ loss_out, float* __restrict__ dscores) {
     __shared__ float part[4];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const float invT = 1.0f / T;
+    // scores / T as the reference divides (kd_manager.py:7-8): a multiplication by the rounded 1 / T is off by up to |x| / T * 2^-24 in the
+    // logit for a T that is no power of two -- 2e-5 at |x| = 2000, T = 3, which the softmax turns into a relative error of that size
     float acc = 0.f;
     for (int r = wid; r < n; r += 4) {
         const float* s = scores + (int64_t)r * c;
         const float* t = target + (int64_t)r * c;
         float ms = -INFINITY, mt = -INFINITY;
         for (int j = lane; j < c; j += 64) {
-            ms = fmaxf(ms, s[j] * invT);
-            mt = fmaxf(mt, t[j] * invT);
+            ms = fmaxf(ms, s[j] / T);
+            mt = fmaxf(mt, t[j] / T);
         }
         ms = wave_max(ms);
         mt = wave_max(mt);
         float ss = 0.f, st = 0.f;
         for (int j = lane; j < c; j += 64) {
-            ss += expf(s[j] * invT - ms);
-            st += expf(t[j] * invT - mt);
+            ss += expf(s[j] / T - ms);
+            st += expf(t[j] / T - mt);
         }
         ss = wave_sum(ss);
         st = wave_sum(st);
         const float lse = logf(ss) + ms, inv_s = 1.0f / ss, inv_t = 1.0f / st;
         float row = 0.f;
         for (int j = lane; j < c; j += 64) {
-            const float pt = expf(t[j] * invT - mt) * inv_t;
-            row -= pt * (s[j] * invT - lse);
-            if (dscores) dscores[(int64_t)r * c + j] = (expf(s[j] * invT - ms) * inv_s - pt) * T / (float)n;
+            const float pt = expf(t[j] / T - mt) * inv_t;
+            row -= pt * (s[j] / T - lse);
+            if (dscores) dscores[(int64_t)r * c + j] = (expf(s[j] / T - ms) * inv_s - pt) * T / (float)n;
         }
         acc += wave_sum(row);
     }
@@ -299,9 +399,10 @@ __global__ void __launch_bounds__(256) mir_kernel(const float* __restrict__ pre,
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int r = blockIdx.x * 4 + wid;
     if (r >= n) return;
-    const float a = ce_row(pre + (int64_t)r * c, c, y[r], lane, nullptr, 1.f);
-    const float b = ce_row(post + (int64_t)r * c, c, y[r], lane, nullptr, 1.f);
-    if (lane == 0) out[r] = b - a;
+    double a, b;
+    ce_row(pre + (int64_t)r * c, c, y[r], lane, nullptr, 1.f, &a);
+    ce_row(post + (int64_t)r * c, c, y[r], lane, nullptr, 1.f, &b);
+    if (lane == 0) out[r] = (float)(b - a);
 }
 
 // =====================================================================================================
@@ -318,7 +419,7 @@ __global__ void __launch_bounds__(256) supcon_rows(const float* __restrict__ fea
     for (int d = threadIdx.x; d < dim; d += blockDim.x) fi[d] = feat[(int64_t)i * dim + d];
     __syncthreads();
     float m = -INFINITY;
-    const bool vec = (dim & 3) == 0 && (((uintptr_t)feat) & 15) == 0;
+    const bool vec = supcon_vec(feat, dim);
     for (int j = threadIdx.x; j < A; j += blockDim.x) {
         const float* fj = feat + (int64_t)j * dim;
         float dot = 0.f;
@@ -358,9 +459,12 @@ __global__ void __launch_bounds__(256) supcon_rows(const float* __restrict__ fea
     if (threadIdx.x == 0) rowloss[i] = -(sp / np);  // 0/0 -> NaN like the reference (loss.py:90)
     if (G) {
         const float invA = 1.0f / (float)A, invden = 1.0f / se, invnp = 1.0f / np;
+        // an anchor without a positive: the reference's autograd sends the 1/0 of loss.py:90 through the zero mask (0 * inf) into every
+        // logit of the row, diagonal included; supcon_grad's symmetrised sum then spreads the NaN to every feature row, as autograd does
+        const bool nopos = np == 0.f;
         for (int j = threadIdx.x; j < A; j += blockDim.x) {
-            float g = 0.f;
-            if (j != i) {
+            float g = nopos ? NAN : 0.f;
+            if (j != i && !nopos) {
                 const float p = expf(lg[j] - m) * invden;
                 const float pos = (y[j % bsz] == yi) ? invnp : 0.f;
                 g = (p - pos) * invA;
@@ -423,7 +527,15 @@ __device__ __forceinline__ bool key_less(float ka, int ia, float kb, int ib) {
     return (ka < kb) || (ka == kb && ia < ib);
 }
 
+// the same order with NaN keys before every number (index order among themselves): argsort's NaN-first rule
+__device__ __forceinline__ bool key_less_nan_first(float ka, int ia, float kb, int ib) {
+    const bool na = isnan(ka), nb = isnan(kb);
+    if (na || nb) return na && (!nb || ia < ib);
+    return key_less(ka, ia, kb, ib);
+}
+
 // in-LDS bitonic sort of P (pow2) (key, idx) pairs, ascending by (key, idx)
+template <bool NAN_FIRST = false>
 __device__ __forceinline__ void bitonic_sort_lds(float* key, int* idx, int P) {
     for (int k = 2; k <= P; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -434,7 +546,7 @@ __device__ __forceinline__ void bitonic_sort_lds(float* key, int* idx, int P) {
                 const bool up = ((lo & k) == 0);
                 const float ka = key[lo], kb = key[hi];
                 const int ia = idx[lo], ib = idx[hi];
-                const bool lt = key_less(kb, ib, ka, ia);  // hi < lo
+                const bool lt = NAN_FIRST ? key_less_nan_first(kb, ib, ka, ia) : key_less(kb, ib, ka, ia);  // hi < lo
                 if (lt == up) {
                     key[lo] = kb; key[hi] = ka;
                     idx[lo] = ib; idx[hi] = ia;
@@ -465,7 +577,7 @@ __global__ void __launch_bounds__(256) knn_sv_kernel(const float* __restrict__ e
     // squared Euclidean distance sum((u-v)^2) (utils/utils.py:93-95): one THREAD per candidate, its feature row streamed with four
     // independent 16-byte loads in flight (rows are L2-resident: every workgroup reads the same candidates), the evaluation row
     // broadcast from LDS.  (One wave per candidate with a shuffle reduction made every step a dependent ~0.5 us L2 round trip.)
-    if ((dim & 3) == 0 && (((uintptr_t)cand_f) & 15) == 0) {
+    if (knn_vec(cand_f, dim)) {
         const int d4n = dim >> 2;
         for (int c = threadIdx.x; c < n_cand; c += blockDim.x) {
             const float4* cf = (const float4*)(cand_f + (int64_t)c * dim);
@@ -619,15 +731,14 @@ __global__ void __launch_bounds__(256) argsort_desc_kernel(const float* __restri
     int* idx = (int*)(key + P);
     for (int i = threadIdx.x; i < P; i += blockDim.x) {
         if (i < n) {
-            float x = v[i];
-            key[i] = isnan(x) ? -INFINITY : -x;  // NaN sorts first in torch's descending order
+            key[i] = -v[i];  // NaN stays NaN: first in torch's descending order, before +inf (key_less_nan_first)
             idx[i] = i;
         } else {
             key[i] = INFINITY;
             idx[i] = 0x7fffffff;
         }
     }
-    bitonic_sort_lds(key, idx, P);
+    bitonic_sort_lds<true>(key, idx, P);
     for (int i = threadIdx.x; i < n; i += blockDim.x) out[i] = (int64_t)idx[i];
 }
 
@@ -912,12 +1023,6 @@ __global__ void __launch_bounds__(64) gemm_small_kernel(const float* __restrict_
 // =====================================================================================================
 // C entry points
 // =====================================================================================================
-static int next_pow2(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 extern "C" {
 
 int ocl_gather_rows(const void* src, const int64_t* idx, int64_t n, int64_t row_bytes, void* dst, void* stream) {
@@ -938,17 +1043,15 @@ int ocl_gather_rows_pair(const void* src_a, int64_t row_bytes_a, void* dst_a, co
         int rc = ocl::upload_small(idx_host, (size_t)n * sizeof(int64_t), idx_dev, s);
         if (rc != OCL_OK) return rc;
     }
-    const bool v16 = (row_bytes_a % 16) == 0 && (((uintptr_t)src_a | (uintptr_t)dst_a) % 16) == 0;
-    if (!v16) {
+    const SPlan pl = plan_pair(src_a, dst_a, row_bytes_a, row_bytes_b, n);
+    if (pl.path == OCL_PATH_PAIR_FALLBACK) {
         int rc = rows_copy<false>(src_a, idx_dev, n, row_bytes_a, dst_a, stream);
         if (rc != OCL_OK) return rc;
         return rows_copy<false>(src_b, idx_dev, n, row_bytes_b, dst_b, stream);
     }
     ProfScope ps(PROF_KNN, s);
-    const int64_t units = row_bytes_a / 16;
-    dim3 grid((unsigned)n, (unsigned)max((int64_t)1, min((int64_t)8, (units + 1023) / 1024)));
-    hipLaunchKernelGGL(rows_gather_pair, grid, dim3(256), 0, s, (const uint4*)src_a, (uint4*)dst_a, units, (const uint32_t*)src_b,
-                       (uint32_t*)dst_b, row_bytes_b / 4, idx_dev);
+    hipLaunchKernelGGL(rows_gather_pair, dim3(pl.grid_x, pl.grid_y), dim3(pl.block), 0, s, (const uint4*)src_a, (uint4*)dst_a, row_bytes_a / 16,
+                       (const uint32_t*)src_b, (uint32_t*)dst_b, row_bytes_b / 4, idx_dev);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -960,9 +1063,8 @@ int ocl_gather_u8_hwc_to_f32_chw(const uint8_t* src, const int64_t* idx, int64_t
     OCL_REQUIRE(src && idx && dst, "gather_u8: null pointer");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_KNN, s);
-    const int64_t per = (int64_t)h * w * c;
-    dim3 grid((unsigned)n, (unsigned)max((int64_t)1, min((int64_t)16, (per + 2047) / 2048)));
-    hipLaunchKernelGGL(gather_u8_hwc_f32_chw, grid, dim3(256), 0, s, src, idx, h, w, c, dst);
+    const SPlan pl = plan_u8(n, h, w, c);
+    hipLaunchKernelGGL(gather_u8_hwc_f32_chw, dim3(pl.grid_x, pl.grid_y), dim3(pl.block), 0, s, src, idx, h, w, c, dst);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -973,29 +1075,28 @@ int ocl_sgd_step(float* params, const float* grads, int64_t n, float lr, float w
     // a backward whose one-pass BatchNorm timed out has poisoned `grads` with NaN: refuse the step instead of applying it (the word
     // is read without synchronising; a time-out that lands after this check is caught by the next forward, before its step)
     if (int arc = ocl::check_async_error("sgd_step")) return arc;
-    OCL_REQUIRE((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)out) % 16) == 0, "sgd: pointers must be 16-B aligned");
+    const SPlan pl = plan_sgd(params, grads, out, n);
+    OCL_REQUIRE(pl.path != OCL_PATH_SGD_REFUSED, "sgd: pointers must be 16-B aligned");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_BN, s);
-    const int blocks = (int)min((int64_t)2048, (n / 4 + 255) / 256 + 1);
-    hipLaunchKernelGGL(sgd_flat, dim3(blocks), dim3(256), 0, s, params, grads, n, lr, weight_decay, grad_scale, out);
+    hipLaunchKernelGGL(sgd_flat, dim3(pl.grid_x), dim3(pl.block), 0, s, params, grads, n, lr, weight_decay, grad_scale, out);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
 
-constexpr int kCosMaxBlocks = 512;
 int64_t ocl_cosine_max_workspace_bytes(int k) { return (int64_t)kCosMaxBlocks * (2 * (int64_t)k + 1) * 8; }
 
 int ocl_cosine_max(const float* mem, int k, int64_t n, const float* g, float eps, float* out, void* workspace, void* stream) {
     OCL_REQUIRE(mem && g && out && workspace && k > 0 && n > 0, "cosine_max: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_KNN, s);
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(kCosMaxBlocks, (n / 4 + 256 * kCosChunk - 1) / (256 * kCosChunk)));
-    if (n % 4 == 0 && ((uintptr_t)mem % 16) == 0 && ((uintptr_t)g % 16) == 0)
-        hipLaunchKernelGGL(cosine_partial_kernel<true>, dim3(blocks), dim3(256), 0, s, mem, k, n, g, (double*)workspace);
+    const SPlan pl = plan_cosine(mem, g, k, n);
+    if (pl.path >= OCL_PATH_COS_VEC_ONE && pl.path <= OCL_PATH_COS_VEC_CAP)
+        hipLaunchKernelGGL(cosine_partial_kernel<true>, dim3(pl.grid_x), dim3(pl.block), 0, s, mem, k, n, g, (double*)workspace);
     else
-        hipLaunchKernelGGL(cosine_partial_kernel<false>, dim3(blocks), dim3(256), 0, s, mem, k, n, g, (double*)workspace);
+        hipLaunchKernelGGL(cosine_partial_kernel<false>, dim3(pl.grid_x), dim3(pl.block), 0, s, mem, k, n, g, (double*)workspace);
     OCL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cosine_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)workspace, blocks, k, eps, out);
+    hipLaunchKernelGGL(cosine_finish_kernel, dim3(pl.grid2_x), dim3(pl.block2), 0, s, (const double*)workspace, pl.aux, k, eps, out);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -1006,7 +1107,8 @@ int ocl_ce_fwd_bwd(const float* logits, const int64_t* y, int n, int c, int redu
     OCL_REQUIRE(reduction == 0 || reduction == 1, "ce: reduction must be 0 (none) or 1 (mean)");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_HEAD, s);
-    hipLaunchKernelGGL(ce_kernel, dim3(1), dim3(256), 0, s, logits, y, n, c, reduction, loss_out, dlogits);
+    const SPlan pl = plan_ce(reduction ? OCL_PATH_CE_MEAN : OCL_PATH_CE_NONE);
+    hipLaunchKernelGGL(ce_kernel, dim3(pl.grid_x), dim3(pl.block), 0, s, logits, y, n, c, reduction, loss_out, dlogits);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -1016,7 +1118,8 @@ int ocl_ce_segmented_fwd_bwd(const float* logits, const int64_t* y, const int32_
     OCL_REQUIRE(logits && y && seg && loss_out && n > 0 && c > 0, "ce_segmented: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_HEAD, s);
-    hipLaunchKernelGGL(ce_seg_kernel, dim3(1), dim3(256), 0, s, logits, y, seg, n, c, loss_out, dlogits);
+    const SPlan pl = plan_ce(OCL_PATH_CE_SEG);
+    hipLaunchKernelGGL(ce_seg_kernel, dim3(pl.grid_x), dim3(pl.block), 0, s, logits, y, seg, n, c, loss_out, dlogits);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -1026,7 +1129,8 @@ int ocl_kd_fwd_bwd(const float* scores, const float* target_scores, int n, int c
     OCL_REQUIRE(scores && target_scores && loss_out && n > 0 && c > 0 && T > 0.f, "kd: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_HEAD, s);
-    hipLaunchKernelGGL(kd_kernel, dim3(1), dim3(256), 0, s, scores, target_scores, n, c, T, loss_out, dscores);
+    const SPlan pl = plan_ce(OCL_PATH_KD);
+    hipLaunchKernelGGL(kd_kernel, dim3(pl.grid_x), dim3(pl.block), 0, s, scores, target_scores, n, c, T, loss_out, dscores);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -1036,7 +1140,8 @@ int ocl_mir_scores(const float* logits_pre, const float* logits_post, const int6
     OCL_REQUIRE(logits_pre && logits_post && y && scores_out && n > 0 && c > 0, "mir_scores: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_KNN, s);
-    hipLaunchKernelGGL(mir_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, logits_pre, logits_post, y, n, c, scores_out);
+    const SPlan pl = plan_mir(n);
+    hipLaunchKernelGGL(mir_kernel, dim3(pl.grid_x), dim3(pl.block), 0, s, logits_pre, logits_post, y, n, c, scores_out);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -1049,16 +1154,16 @@ int ocl_supcon_fwd_bwd(const float* feat, const int64_t* y, int bsz, int n_views
                        float* dfeat, void* workspace, void* stream) {
     OCL_REQUIRE(feat && y && loss_out && workspace, "supcon: null pointer");
     OCL_REQUIRE(bsz > 0 && n_views > 0 && dim > 0 && temperature > 0.f, "supcon: bad shape/temperature");
+    const SPlan pl = plan_supcon(feat, bsz, n_views, dim, dfeat != nullptr);
+    OCL_REQUIRE(pl.path != OCL_PATH_SUPCON_REFUSED, "supcon: A=%lld dim=%d too large", (long long)bsz * n_views, dim);
     const int A = bsz * n_views;
-    OCL_REQUIRE(A <= 8192 && dim <= 4096, "supcon: A=%d dim=%d too large", A, dim);
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_HEAD, s);
     float* G = (float*)workspace;
     float* rowloss = G + (int64_t)A * A;
-    const size_t sm = (size_t)(dim + A + 16) * sizeof(float);
-    hipLaunchKernelGGL(supcon_rows, dim3(A), dim3(256), sm, s, feat, y, bsz, A, dim, temperature, G, rowloss);
+    hipLaunchKernelGGL(supcon_rows, dim3(pl.grid_x), dim3(pl.block), (size_t)pl.lds_bytes, s, feat, y, bsz, A, dim, temperature, G, rowloss);
     OCL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(supcon_grad, dim3(dfeat ? A : 1), dim3(128), (size_t)std::max(A, 128) * sizeof(float), s, feat, A, dim, temperature, G, rowloss,
+    hipLaunchKernelGGL(supcon_grad, dim3(pl.grid2_x), dim3(pl.block2), (size_t)pl.lds2_bytes, s, feat, A, dim, temperature, G, rowloss,
                        loss_out, dfeat);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
@@ -1070,12 +1175,11 @@ int ocl_knn_sv(const float* eval_f, const int64_t* eval_y, int n_eval, const flo
                 n_cand, dim, k);
     if (n_eval == 0 || n_cand == 0) return OCL_OK;
     OCL_REQUIRE(eval_f && eval_y && cand_f && cand_y && sv_out, "knn_sv: null pointer");
-    OCL_REQUIRE(n_cand <= OCL_KNN_MAX_CAND, "knn_sv: n_cand=%d exceeds OCL_KNN_MAX_CAND=%d", n_cand, OCL_KNN_MAX_CAND);
+    const SPlan pl = plan_knn(cand_f, n_eval, n_cand, dim);
+    OCL_REQUIRE(pl.path != OCL_PATH_KNN_REFUSED, "knn_sv: n_cand=%d exceeds OCL_KNN_MAX_CAND=%d", n_cand, OCL_KNN_MAX_CAND);
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_KNN, s);
-    const int P = next_pow2(n_cand);
-    const size_t sm = (size_t)P * (8 + 4 + 4) + (size_t)dim * 4;
-    hipLaunchKernelGGL(knn_sv_kernel, dim3(n_eval), dim3(256), sm, s, eval_f, eval_y, cand_f, cand_y, n_cand, dim, k, P, sv_out,
+    hipLaunchKernelGGL(knn_sv_kernel, dim3(pl.grid_x), dim3(pl.block), (size_t)pl.lds_bytes, s, eval_f, eval_y, cand_f, cand_y, n_cand, dim, k, pl.aux, sv_out,
                        sorted_idx);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
@@ -1085,7 +1189,8 @@ int ocl_col_reduce(const float* m, int rows, int cols, int mode, float* out, voi
     OCL_REQUIRE(m && out && rows > 0 && cols > 0 && mode >= 0 && mode <= 3, "col_reduce: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_KNN, s);
-    hipLaunchKernelGGL(col_reduce_kernel, dim3(cdiv(cols, 32)), dim3(256), 0, s, m, rows, cols, mode, out);
+    const SPlan pl = plan_cols(OCL_PATH_COL_REDUCE, cols);
+    hipLaunchKernelGGL(col_reduce_kernel, dim3(pl.grid_x), dim3(pl.block), 0, s, m, rows, cols, mode, out);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -1096,7 +1201,8 @@ int ocl_aser_score(const float* sv_adv, int n_adv, const float* sv_coop, int n_c
     OCL_REQUIRE(type == 2 || (sv_coop && n_coop > 0), "aser_score: cooperative matrix required for type %d", type);
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_KNN, s);
-    hipLaunchKernelGGL(aser_score_kernel, dim3(cdiv(n_cand, 32)), dim3(256), 0, s, sv_adv, n_adv, sv_coop, n_coop, n_cand, type,
+    const SPlan pl = plan_cols(OCL_PATH_ASER_SCORE, n_cand);
+    hipLaunchKernelGGL(aser_score_kernel, dim3(pl.grid_x), dim3(pl.block), 0, s, sv_adv, n_adv, sv_coop, n_coop, n_cand, type,
                        out);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
@@ -1106,11 +1212,11 @@ int ocl_argsort_desc(const float* v, int n, int64_t* idx_out, void* stream) {
     OCL_REQUIRE(n >= 0, "argsort: n<0");
     if (n == 0) return OCL_OK;
     OCL_REQUIRE(v && idx_out, "argsort: null pointer");
-    OCL_REQUIRE(n <= OCL_SORT_MAX, "argsort: n=%d exceeds OCL_SORT_MAX=%d", n, OCL_SORT_MAX);
+    const SPlan pl = plan_argsort(n);
+    OCL_REQUIRE(pl.path != OCL_PATH_ARGSORT_REFUSED, "argsort: n=%d exceeds OCL_SORT_MAX=%d", n, OCL_SORT_MAX);
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_KNN, s);
-    const int P = next_pow2(n);
-    hipLaunchKernelGGL(argsort_desc_kernel, dim3(1), dim3(256), (size_t)P * 8, s, v, n, P, idx_out);
+    hipLaunchKernelGGL(argsort_desc_kernel, dim3(pl.grid_x), dim3(pl.block), (size_t)pl.lds_bytes, s, v, n, pl.aux, idx_out);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -1120,7 +1226,8 @@ int ocl_ncm_class_means(const float* feat, const int64_t* labels, int n, int d, 
     OCL_REQUIRE(feat && labels && class_ids && means_out && n >= 0 && d > 0 && n_cls > 0, "ncm_means: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_KNN, s);
-    hipLaunchKernelGGL(ncm_means_kernel, dim3(n_cls), dim3(256), (size_t)d * 8 + 64, s, feat, labels, n, d, class_ids, means_out,
+    const SPlan pl = plan_ncm_means(d, n_cls);
+    hipLaunchKernelGGL(ncm_means_kernel, dim3(pl.grid_x), dim3(pl.block), (size_t)pl.lds_bytes, s, feat, labels, n, d, class_ids, means_out,
                        counts_out);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
@@ -1132,7 +1239,8 @@ int ocl_ncm_predict(const float* feat, int n, int d, const float* means, int n_c
     OCL_REQUIRE(feat && means && pred_out, "ncm_predict: null pointer");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_KNN, s);
-    hipLaunchKernelGGL(ncm_predict_kernel, dim3(n), dim3(256), (size_t)(d + n_cls + 16) * 4, s, feat, d, means, n_cls, pred_out);
+    const SPlan pl = plan_ncm_predict(n, d, n_cls);
+    hipLaunchKernelGGL(ncm_predict_kernel, dim3(pl.grid_x), dim3(pl.block), (size_t)pl.lds_bytes, s, feat, d, means, n_cls, pred_out);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -1180,10 +1288,43 @@ int ocl_gemm_small(const float* a, int64_t a_rs, int64_t a_cs, const float* b, i
     OCL_REQUIRE(a && b && c && m > 0 && n > 0 && k > 0, "gemm_small: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_HEAD, s);
-    hipLaunchKernelGGL(gemm_small_kernel, dim3(cdiv(n, 16), cdiv(m, 16)), dim3(64), 0, s, a, a_rs, a_cs, b, b_rs, b_cs, c, c_rs, m,
+    const SPlan pl = plan_gemm(m, n, k);
+    hipLaunchKernelGGL(gemm_small_kernel, dim3(pl.grid_x, pl.grid_y), dim3(pl.block), 0, s, a, a_rs, a_cs, b, b_rs, b_cs, c, c_rs, m,
                        n, k, bias, relu, accumulate);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
+}
+
+int ocl_test_small_op_path(int op, const int64_t* a, int na, ocl_small_op_plan* plan) {
+    static const int kArgs[] = {4, 5, 4, 4, 4, 3, 2, 2, 2, 5, 5, 2, 1, 1, 2, 3, 3};
+    const int n_ops = (int)(sizeof(kArgs) / sizeof(kArgs[0]));
+    if (op < 0 || op >= n_ops || !a || na != kArgs[op]) {
+        ocl::set_error("small_op_path: op %d takes %d arguments, got %d", op, op >= 0 && op < n_ops ? kArgs[op] : -1, na);
+        return 0;
+    }
+    auto P = [&](int i) { return (const void*)(uintptr_t)a[i]; };
+    SPlan p;
+    switch (op) {
+        case OCL_SOP_ROWS: p = plan_rows(P(0), P(1), a[2], a[3]); break;
+        case OCL_SOP_PAIR: p = plan_pair(P(0), P(1), a[2], a[3], a[4]); break;
+        case OCL_SOP_U8: p = plan_u8(a[0], (int)a[1], (int)a[2], (int)a[3]); break;
+        case OCL_SOP_SGD: p = plan_sgd(P(0), P(1), P(2), a[3]); break;
+        case OCL_SOP_COSINE: p = plan_cosine(P(0), P(1), (int)a[2], a[3]); break;
+        case OCL_SOP_CE: p = plan_ce(a[2] ? OCL_PATH_CE_MEAN : OCL_PATH_CE_NONE); break;
+        case OCL_SOP_CE_SEG: p = plan_ce(OCL_PATH_CE_SEG); break;
+        case OCL_SOP_KD: p = plan_ce(OCL_PATH_KD); break;
+        case OCL_SOP_MIR: p = plan_mir((int)a[0]); break;
+        case OCL_SOP_SUPCON: p = plan_supcon((const float*)P(0), (int)a[1], (int)a[2], (int)a[3], a[4] != 0); break;
+        case OCL_SOP_KNN: p = plan_knn((const float*)P(0), (int)a[1], (int)a[2], (int)a[3]); break;
+        case OCL_SOP_COL_REDUCE: p = plan_cols(OCL_PATH_COL_REDUCE, (int)a[1]); break;
+        case OCL_SOP_ASER: p = plan_cols(OCL_PATH_ASER_SCORE, (int)a[0]); break;
+        case OCL_SOP_ARGSORT: p = plan_argsort((int)a[0]); break;
+        case OCL_SOP_NCM_MEANS: p = plan_ncm_means((int)a[0], (int)a[1]); break;
+        case OCL_SOP_NCM_PREDICT: p = plan_ncm_predict((int)a[0], (int)a[1], (int)a[2]); break;
+        default: p = plan_gemm((int)a[0], (int)a[1], (int)a[2]); break;
+    }
+    if (plan) *plan = p;
+    return p.path;
 }
 
 }  // extern "C"

@@ -77,6 +77,12 @@ class TestNetForm(C.Structure):
                                                                    ("wdesc", TestWgradDesc), ("wform", TestWgradForm)]
 
 
+class SmallOpPlan(C.Structure):
+    """ocl_small_op_plan: what ocl_test_small_op_path reports (tests/test_cpu_small_ops.py, tests/test_gpu_small_ops.py)."""
+    _fields_ = [("path", i32), ("aux", i32), ("grid_x", C.c_uint32), ("grid_y", C.c_uint32), ("block", C.c_uint32),
+                ("grid2_x", C.c_uint32), ("block2", C.c_uint32), ("reserved", C.c_uint32), ("lds_bytes", i64), ("lds2_bytes", i64)]
+
+
 # name -> (restype, argtypes); kept in one table so tests can check it against the header
 SIGNATURES = {
     "ocl_version": (C.c_int, []),
@@ -133,6 +139,7 @@ SIGNATURES = {
     "ocl_test_bn_bwd": (C.c_int, [C.POINTER(TestBnBwdArgs), vp]),
     "ocl_test_bn_apply_e": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     "ocl_test_net_forms": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TestNetForm), C.c_int]),
+    "ocl_test_small_op_path": (C.c_int, [C.c_int, C.POINTER(i64), C.c_int, C.POINTER(SmallOpPlan)]),
     "ocl_prof_enable": (C.c_int, [C.c_int]),
     "ocl_prof_reset": (C.c_int, []),
     "ocl_prof_query": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(i64)]),
@@ -151,7 +158,7 @@ OCL_CONV_PIPE OCL_CONV_Q4 OCL_CONV_S OCL_CONV_S_NT OCL_CONV_W OCL_CONV_WX OCL_DA
 OCL_DEBUG_SKIP_WGRAD OCL_DETERMINISTIC OCL_DIST_BACKEND OCL_DY_KEEP OCL_GC_FREEZE OCL_GRAPH OCL_GRAPH_VERBOSE OCL_LIB OCL_LOG_PLANS
 OCL_PIN OCL_SIDE_EXTRA_MIN OCL_SINGLE_STREAM OCL_WGRAD_ENOUGH OCL_WGRAD_FLUSH OCL_WGRAD_MULTI OCL_WGRAD_MULTI_TARGET OCL_WGRAD_Q
 OCL_WGRAD_TARGET""".split())
-HARNESS_ENV = frozenset("OCL_NONE OCL_TEST_CASES OCL_TEST_PORT OCL_SHARD_BACKEND OCL_PROBE_STREAM OCL_EAGER_DEVICE".split())
+HARNESS_ENV = frozenset("OCL_NONE OCL_TEST_CASES OCL_TEST_PORT OCL_SHARD_BACKEND OCL_PROBE_STREAM OCL_EAGER_DEVICE OCL_PARITY_REPORT".split())
 
 
 def unknown_env(environ=None):

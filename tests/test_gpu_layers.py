@@ -22,13 +22,12 @@ import torch
 import torch.nn.functional as F
 
 import layer_forms as LF
+from guarded import FILL, SLACK, assert_slack_untouched, dev   # (shared with test_gpu_small_ops.py)
 
 pytestmark = pytest.mark.gpu
 
 EPI_STATS, EPI_AFFINE, EPI_RES, EPI_RESMASK, EPI_RELU, EPI_ACCUM, EPI_BNB = 1, 2, 4, 8, 16, 32, 64
 U = 2.0 ** -24
-SLACK = 1 << 16          # elements of slack behind every device tensor (plans may read a padded channel split past a tensor's end)
-FILL = 4096              # what the slack holds: finite (a padded read times a zero weight still cancels), but visible if it is accumulated
 
 
 @pytest.fixture(scope="module")
@@ -38,20 +37,6 @@ def lib(cuda):
     torch.set_num_threads(16)
     yield L
     L.ocl_set_deterministic(0)
-
-
-def dev(t):
-    """A cuda copy of t (float32 / int64) with SLACK elements of FILL behind it."""
-    t = t.contiguous()
-    buf = torch.full((t.numel() + SLACK,), FILL, dtype=t.dtype, device="cuda")
-    buf[: t.numel()].copy_(t.reshape(-1))
-    return buf[: t.numel()].view(t.shape)
-
-
-def assert_slack_untouched(t, what):
-    """The slack behind a dev() tensor still holds FILL: nothing wrote past the tensor's end."""
-    tail = t._base[t.numel():]
-    assert bool((tail == FILL).all()), "%s: %d elements written past the end" % (what, int((tail != FILL).sum()))
 
 
 def cells(reps_groups_c):

@@ -71,6 +71,20 @@ int ocl_gather_u8_hwc_to_f32_chw(const uint8_t* src, const int64_t* idx, int64_t
 int ocl_sgd_step(float* params, const float* grads, int64_t n, float lr, float weight_decay,
                  float grad_scale, float* out, void* stream);
 
+/* ---- K8b: Adam -----------------------------------------------------------------------------------
+ * torch.optim.Adam.step (utils/setup_elements.py:76-79: betas (0.9, 0.999), eps 1e-8, amsgrad off) over the
+ * flat parameter, gradient and moment arrays, one launch, in the order of torch's _single_tensor_adam:
+ *   g' = wd*p + g*grad_scale;  m <- m + (1-beta1)*(g'-m);  v <- beta2*v + (1-beta2)*g'*g';
+ *   p <- p - step_size * (m / (sqrt(v)/bc2_sqrt + eps)),  step_size = lr/(1-beta1^step), bc2_sqrt = sqrt(1-beta2^step).
+ * `step` is this step's 1-based number; step_size, bc2_sqrt and 1-beta are formed in double on the host from
+ * the float arguments (no device-side counter, no synchronisation).  Elements [skip_begin, skip_end) keep p, m
+ * and v: parameters that never get a gradient, which torch skips entirely (SupConResNet's encoder.linear.*).
+ * All four arrays 16-byte aligned; OCL_ERR_ARG before any launch for a null or misaligned pointer, n <= 0,
+ * step < 1, a beta outside [0, 1), eps < 0, or a skip range that is not 0 <= begin <= end <= n. */
+int ocl_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                  float beta1, float beta2, float eps, float weight_decay, float grad_scale, int64_t step,
+                  int64_t skip_begin, int64_t skip_end, void* stream);
+
 /* ---- K6: softmax cross-entropy ---------------------------------------------------------------------
  * torch.nn.CrossEntropyLoss(reduction='mean') (agents/base.py:95,113) and
  * F.cross_entropy(reduction='none') (utils/buffer/mir_retrieve.py:26-27).

@@ -139,6 +139,21 @@ def sgd_step(params_flat, grads_flat, lr, weight_decay=0.0, grad_scale=1.0, out=
     return out if out is not None else params_flat
 
 
+# ---- K8b ---------------------------------------------------------------------------------------------
+def adam_step(params_flat, grads_flat, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0,
+              skip=(0, 0)):
+    """One torch.optim.Adam step (amsgrad off) over the flat arrays, in place; `step` is this step's 1-based number, elements
+    skip[0] .. skip[1] - 1 are left untouched."""
+    ffi.init()
+    for t in (grads_flat, exp_avg, exp_avg_sq):
+        if t.dtype != torch.float32 or params_flat.dtype != torch.float32 or t.numel() != params_flat.numel() or t.device != params_flat.device:
+            raise RuntimeError("adam_step: four float32 arrays of one length on one device")
+    ffi.check(ffi.lib().ocl_adam_step(ffi.ptr(params_flat), ffi.ptr(grads_flat), ffi.ptr(exp_avg), ffi.ptr(exp_avg_sq), params_flat.numel(),
+                                      float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale),
+                                      int(step), int(skip[0]), int(skip[1]), ffi.stream()), "adam_step")
+    return params_flat
+
+
 # ---- K6 ----------------------------------------------------------------------------------------------
 def cross_entropy(logits, y, reduction="mean", want_grad=True, dl_out=None):
     """(loss, dlogits): torch.nn.CrossEntropyLoss / F.cross_entropy(reduction='none').  dl_out: a contiguous float32 [n, c] tensor

@@ -191,7 +191,7 @@ class _EngineMixin:
         return self._gflat
 
     def mark_weights_written(self):
-        """The bound parameter array was written through the engine (FusedSGD.step): the next forward re-packs."""
+        """The bound parameter array was written through the engine (FusedSGD.step, FusedAdam.step): the next forward re-packs."""
         self._weights_dirty = True
 
     @contextlib.contextmanager
@@ -199,7 +199,7 @@ class _EngineMixin:
         """Inside the block, a forward that follows another forward of the block with no write to the parameters in between carries
         OCL_FWD_SAME_WEIGHTS: the engine reuses the weight packs it made for the earlier one (agents/exp_replay.py: the ASER update's
         feature pass, the batch pass, the retrieval's feature pass, the memory pass and the combined pass between two optimiser steps).
-        "No write" is checked, not assumed: FusedSGD.step() reports itself, and every torch in-place write to a parameter or to the
+        "No write" is checked, not assumed: FusedSGD.step() / FusedAdam.step() report themselves, and every torch in-place write to a parameter or to the
         flat array (load_state_dict, copy_, mul_ ...) moves a version counter that is compared here.  What the counters cannot see is
         a write through `p.data` -- do not do that inside such a block (nothing in this package does)."""
         prev, self._same_weights = self._same_weights, True

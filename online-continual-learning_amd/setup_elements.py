@@ -3,7 +3,7 @@ import torch
 import torch.nn as nn
 
 from .resnet import Reduced_ResNet18, SupConResNet
-from .optim import FusedSGD
+from .optim import FusedSGD, FusedAdam
 
 default_trick = {'labels_trick': False, 'kd_trick': False, 'separated_softmax': False,
                  'review_trick': False, 'ncm_trick': False, 'kd_trick_star': False}
@@ -44,11 +44,11 @@ def setup_architecture(params):
 
 
 def setup_opt(optimizer, model, lr, wd):
-    """utils/setup_elements.py:71-82.  'SGD' returns the fused single-kernel optimiser (same update rule as
-    torch.optim.SGD with momentum 0)."""
+    """utils/setup_elements.py:71-82.  Both names return a fused single-kernel optimiser over the model's flat parameter array:
+    'SGD' the update rule of torch.optim.SGD with momentum 0, 'Adam' that of torch.optim.Adam with its defaults."""
     if optimizer == 'SGD':
         return FusedSGD(model, lr=lr, weight_decay=wd)
     elif optimizer == 'Adam':
-        return torch.optim.Adam(model.parameters(), lr=lr, weight_decay=wd)
+        return FusedAdam(model, lr=lr, weight_decay=wd)
     else:
         raise Exception('wrong optimizer name')

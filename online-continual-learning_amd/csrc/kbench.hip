@@ -1124,12 +1124,18 @@ int main(int argc, char** argv) {
                 pro += (double)(r[1] - r[0]);
                 life += (double)(r[last] - r[0]);
                 int e = 1;
-                for (; e + 5 <= last; e += 5) {
-                    for (int k = 0; k < 5; ++k) ph[k] += (double)(r[e + k + 1] - r[e + k]);
+                const int np = wp.q_rgw ? 4 : 5;   // stamps per tile (4x4x1 form: one barrier per tile, see conv_wgrad_body)
+                for (; e + np <= last; e += np) {
+                    for (int k = 0; k < np; ++k) ph[k] += (double)(r[e + k + 1] - r[e + k]);
                     ++ntile;
                 }
                 if (e < last) epi += (double)(r[last] - r[e]);
             }
+            if (wp.q_rgw)
+                printf("%-20s MTW=%d NTW=%d q4=%d grid=%4dx%d tiles/wg=%.1f  span %6llu | per workgroup: prologue + first store %6.0f  lifetime %7.0f  epilogue %6.0f | per tile: barrier %5.0f  next-load issue %5.0f  K loop %6.0f  next-tile store %5.0f  (sum %6.0f ticks)\n",
+                       l.name.c_str(), wp.MTW, wp.NTW, wp.q_rgw, wp.grid_x, wp.grid_y, (double)ntile / nwg, t1 - t0, pro / nwg, life / nwg, epi / nwg,
+                       ph[0] / ntile, ph[1] / ntile, ph[2] / ntile, ph[3] / ntile, (ph[0] + ph[1] + ph[2] + ph[3]) / ntile);
+            else
             printf("%-20s MTW=%d NTW=%d q4=%d grid=%4dx%d tiles/wg=%.1f  span %6llu | per workgroup: prologue %6.0f  lifetime %7.0f  epilogue %6.0f | per tile: barrier1 %5.0f  store %5.0f  barrier2 %5.0f  next-load issue %5.0f  K loop %6.0f  (sum %6.0f ticks)\n",
                    l.name.c_str(), wp.MTW, wp.NTW, wp.q_rgw, wp.grid_x, wp.grid_y, (double)ntile / nwg, t1 - t0, pro / nwg, life / nwg, epi / nwg,
                    ph[0] / ntile, ph[1] / ntile, ph[2] / ntile, ph[3] / ntile, ph[4] / ntile, (ph[0] + ph[1] + ph[2] + ph[3] + ph[4]) / ntile);

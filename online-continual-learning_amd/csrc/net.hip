@@ -609,6 +609,8 @@ static int head_forward(ocl_net* n, const float* P, float* feat, float* h1, floa
     return rc;
 }
 
+// trailing layers of a large pass's backward handed to the weight-gradient stream one by one (OCL_WGRAD_FLUSH_TAIL; trunk_backward)
+constexpr int kWgradFlushTail = 5;
 // projection shortcut / head weight gradients on the side stream from 96 x 32 x 32 input pixels on (OCL_SIDE_EXTRA_MIN: A/B, profiles/r6_side_extra_ab.txt)
 static const int kSideExtraMinBatch = [] { const char* e = getenv("OCL_SIDE_EXTRA_MIN"); return e ? atoi(e) : 96; }();
 
@@ -1139,6 +1141,13 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
     static const int env_flush = [] { const char* e = getenv("OCL_WGRAD_FLUSH"); return e ? std::max(1, atoi(e)) : 0; }();
     const int flush_every = env_flush > 0 ? env_flush : (Nc >= 128 ? 3 : 1);
     const bool coarse = two_streams && keep && flush_every > 1;
+    // ... except at the end of the backward, where the chain is short of what the other stream still has to do: the last
+    // OCL_WGRAD_FLUSH_TAIL layers (in backward order; the stem, which stays on the caller's stream, is the last of them) are handed over
+    // one by one, each as soon as its dL/dy exists, and the last hand-over is issued in front of the stem's BatchNorm backward instead
+    // of behind it.  0: groups of flush_every to the end, the last one behind the stem's BatchNorm backward.
+    static const int env_tail = [] { const char* e = getenv("OCL_WGRAD_FLUSH_TAIL"); return e ? std::max(0, atoi(e)) : kWgradFlushTail; }();
+    const int tail_from = coarse ? n_dy - env_tail : n_dy;   // first layer, in backward order, that is handed over on its own
+    int n_handed = 0;
     std::vector<WgradPlan> deferred;
     auto take_dy = [&](int* slot_out) -> float* {   // next ring slot; the main stream waits for its previous readers
         if (keep) {
@@ -1272,7 +1281,7 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
     auto wgrad = [&](int conv_i, const float* xin, const float* dy, int xf_conv = -1) -> int {
         if (!coarse) return wgrad_now(conv_i, xin, dy, xf_conv);
         pending.push_back({conv_i, xin, dy, xf_conv});
-        return (int)pending.size() >= flush_every ? flush_pending() : OCL_OK;
+        return (n_handed++ >= tail_from || (int)pending.size() >= flush_every) ? flush_pending() : OCL_OK;
     };
     auto dgrad = [&](int conv_i, const float* dy, float* dx, const float* res, const float* resmask, int extra_flags,
                      const BnbEpi* be = nullptr) -> int {
@@ -1384,6 +1393,7 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
         std::swap(gA, gE);
     }
     // stem
+    if (env_tail > 0 && (rc = flush_pending())) return rc;   // (layer1.0.conv1's dL/dy exists: the stem's BatchNorm backward is not waited for)
     int rS;
     float* gS = take_dy(&rS);
     if (prev_epi) {

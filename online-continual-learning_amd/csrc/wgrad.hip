@@ -43,7 +43,8 @@ struct WTile {
 // the pixel table instead of branching around the store.
 // TRACE = 1 (measurement build, kbench `wgradtrace`): s_memtime stamps of thread 0 at the phase boundaries into WgradArgs::trace,
 // 64 slots per workgroup: start | prologue done | per tile: passed barrier 1, tile stored, passed barrier 2, next tile's loads issued,
-// K loop done | ... | slab written.
+// K loop done | ... | slab written.  (4x4x1 form, one barrier per tile: start | first tile stored | per tile: passed the barrier, next tile's
+// loads issued, K loop done, next tile stored | ... | slab written.)
 // (the body takes its workgroup id from the caller: conv_wgrad_kernel passes blockIdx, conv_wgrad_multi_kernel the id inside its layer)
 template <int MTW, int NTW, int PF, int RGW = 0, int TRACE = 0>
 __device__ __forceinline__ void conv_wgrad_body(const WgradArgs& a, const int bid_x, const int bid_y) {
@@ -51,7 +52,11 @@ __device__ __forceinline__ void conv_wgrad_body(const WgradArgs& a, const int bi
     int* pixoff = (int*)lds_raw + 4;                // [KP]   (in front of it: the staging's dummy slot)
     float* dyt = (float*)(pixoff + a.KP);           // [KP][DP]
     float* patch = dyt + (size_t)a.KP * a.DP;       // [imgs][PR][PC][CP]
-    float* xft = patch + (((size_t)a.imgs * a.PR * a.PC * a.CP + 3) & ~(size_t)3);   // input transform (WgradArgs::xf): [groups][Cin/4][2][4] scale / shift quads
+    const size_t patch_floats = ((size_t)a.imgs * a.PR * a.PC * a.CP + 3) & ~(size_t)3;
+    // 4x4x1 form: TWO copies of dummy slot + pixel table + dy tile + patch, `bstride` bytes apart (a store address of buffer 1 is that
+    // of buffer 0 + bstride, dummy slot included); the input-transform table lies behind the second copy
+    const int bstride = RGW > 0 ? (int)(16 + ((size_t)a.KP + (size_t)a.KP * a.DP + patch_floats) * 4) : 0;
+    float* xft = (float*)((unsigned char*)(patch + patch_floats) + bstride);   // input transform (WgradArgs::xf): [groups][Cin/4][2][4] scale / shift quads
     constexpr int BNW = RGW > 0 ? 4 * kQBlocks : 16 * NTW;
     constexpr int Q = BNW / 4;
     constexpr int DPF = (128 * Q + 255) / 256;      // dy prefetch registers (KP <= 128)
@@ -221,10 +226,11 @@ __device__ __forceinline__ void conv_wgrad_body(const WgradArgs& a, const int bi
             okm |= ok ? (1u << i) : 0u;
         }
     };
-    auto store_tile = [&](const WTile& t) __attribute__((always_inline)) {
+    auto store_tile = [&](const WTile& t, const int boff) __attribute__((always_inline)) {   // boff: byte offset of the LDS buffer (0 | bstride)
+        unsigned char* const lb = lds_raw + boff;
 #pragma unroll
-        for (int i = 0; i < DPF; ++i) *(float4*)(dyt + d_lds[i]) = dv[i];
-        pixoff[px_idx] = pxo;
+        for (int i = 0; i < DPF; ++i) *(float4*)((unsigned char*)(dyt + d_lds[i]) + boff) = dv[i];
+        *(int*)((unsigned char*)(pixoff + px_idx) + boff) = pxo;
 #pragma unroll
         for (int i = 0; i < PF; ++i) {
             float4 v = pv[i];
@@ -237,7 +243,7 @@ __device__ __forceinline__ void conv_wgrad_body(const WgradArgs& a, const int bi
                 v.z = fmaxf(__fmaf_rn(v.z, sc.z, sh.z), 0.f); v.w = fmaxf(__fmaf_rn(v.w, sc.w, sh.w), 0.f);
                 if (!((okm >> i) & 1u)) v = make_float4(0.f, 0.f, 0.f, 0.f);
             }
-            float* d = (float*)(lds_raw + (p_lds[i] & 0xffffff));
+            float* d = (float*)(lb + (p_lds[i] & 0xffffff));
             *(float2*)d = make_float2(v.x, v.y);
             *(float2*)(d + 2) = make_float2(v.z, v.w);
         }
@@ -249,10 +255,11 @@ __device__ __forceinline__ void conv_wgrad_body(const WgradArgs& a, const int bi
         }
     };
     // the K loop of the tile that sits in LDS
-    auto compute_tile = [&]() __attribute__((always_inline)) {
+    auto compute_tile = [&](const int boff) __attribute__((always_inline)) {
         if constexpr (RGW > 0) {   // 16 pixels per step (KP is a multiple of 16 in this form); operands of step g + 1 are read while the MFMAs of step g issue
-            const float* dq = dyt + (size_t)(lane >> 2) * a.DP + (lane & 3);
-            const int* pq = pixoff + (lane >> 2);
+            const float* dq = (const float*)((const unsigned char*)dyt + boff) + (size_t)(lane >> 2) * a.DP + (lane & 3);
+            const int* pq = (const int*)((const unsigned char*)pixoff + boff) + (lane >> 2);
+            const float* patchb = (const float*)((const unsigned char*)patch + boff);
             const int ng = a.KP >> 4;
             float bv[2][kQBlocks];
             float4 av[2][RG];
@@ -261,7 +268,7 @@ __device__ __forceinline__ void conv_wgrad_body(const WgradArgs& a, const int bi
                 const int po = po_n;
                 po_n = pq[min(g + 1, ng - 1) * 16];
 #pragma unroll
-                for (int r = 0; r < RG; ++r) av[set][r] = *(const float4*)(patch + po + qoff[r]);
+                for (int r = 0; r < RG; ++r) av[set][r] = *(const float4*)(patchb + po + qoff[r]);
 #pragma unroll
                 for (int s = 0; s < kQBlocks; ++s) bv[set][s] = dq[(size_t)g * 16 * a.DP + 4 * s];
             };
@@ -333,21 +340,46 @@ __device__ __forceinline__ void conv_wgrad_body(const WgradArgs& a, const int bi
     int tile = bx;
     WTile cur = geom(tile);
     if (tile < a.total_tiles) load_tile(cur);
-    stamp();
-    for (; tile < a.total_tiles; tile += a.S) {
-        __syncthreads();  // previous tile consumed
+    if constexpr (RGW > 0) {
+        // Two LDS buffers, ONE barrier per tile: tile n + 1 goes into the other buffer behind the K loop of tile n, so the wait for its
+        // loads and its LDS stores run under the MFMAs still in flight (and beside the K loops of the waves that lag) instead of
+        // between two barriers.  The barrier of tile n says both "buffer n & 1 is written" and "the K loop of tile n - 1, which read
+        // the other buffer, is over".  Same tiles, same pixel order, same accumulators as the one-buffer loop: same bits.
+        if (a.xf) __syncthreads();   // the input-transform table is read by the stores below (block-uniform)
+        if (tile < a.total_tiles) store_tile(cur, 0);
         stamp();
-        store_tile(cur);
-        stamp();
-        __syncthreads();
-        stamp();
-        const int next = tile + a.S;
-        if (next < a.total_tiles) {
-            cur = geom(next);
-            load_tile(cur);
+        int boff = 0;
+        for (; tile < a.total_tiles; tile += a.S) {
+            __syncthreads();
+            stamp();
+            const int next = tile + a.S;
+            if (next < a.total_tiles) {
+                cur = geom(next);
+                load_tile(cur);
+            }
+            stamp();
+            compute_tile(boff);
+            boff = bstride - boff;
+            if (next < a.total_tiles) store_tile(cur, boff);
+            stamp();
         }
+    } else {
         stamp();
-        compute_tile();
+        for (; tile < a.total_tiles; tile += a.S) {
+            __syncthreads();  // previous tile consumed
+            stamp();
+            store_tile(cur, 0);
+            stamp();
+            __syncthreads();
+            stamp();
+            const int next = tile + a.S;
+            if (next < a.total_tiles) {
+                cur = geom(next);
+                load_tile(cur);
+            }
+            stamp();
+            compute_tile(0);
+        }
     }
     // partial tile out: rows (chunk, mblock, m), cols co
     const int mrows_chunk = a.mblocks_per_chunk * 64 * MTW;
@@ -697,16 +729,18 @@ int plan_wgrad(int N, int Hin, int Win, int Cin, int Ho, int Wo, int Cout, int k
     // (the stem's 9 units fill 3 of 4 waves: measured slower; the block sums of the epilogue cost about 1.7 pixel tiles, and the form
     // runs one workgroup per CU: it pays from ~6 tiles of 128 pixels per workgroup at 256 workgroups -- SCR's 220 views yes,
     // 20 images of 84 x 84 no (+40 us); OCL_WGRAD_Q=2 lifts that limit for the planner test)
-    if (env_q && Cout <= 4 * kQBlocks && Cin >= 8 && a.nchunks == 1 && a.CP % 4 == 0 && a.KP % 16 == 0 &&
+    // (two tile buffers -- dummy slot, pixel table, dy tile of 4 * kQBlocks columns, patch each -- and the input-transform table behind
+    // them: conv_wgrad_body; layer 1 at 32 x 32: 2 x 27 KB, and the form runs one workgroup per CU by its accumulators anyway)
+    const size_t qbytes = 2 * (16 + (size_t)a.KP * 4 + (size_t)a.KP * 4 * kQBlocks * 4 + (((size_t)a.imgs * a.PR * a.PC * a.CP + 3) & ~(size_t)3) * 4) +
+                          (size_t)xf_groups * Cin * 8 + (xf_groups ? 16 : 0);
+    if (env_q && Cout <= 4 * kQBlocks && Cin >= 8 && a.nchunks == 1 && a.CP % 4 == 0 && a.KP % 16 == 0 && qbytes <= kLdsLimit &&
         ((int64_t)a.total_tiles * a.KP >= 6 * 128 * 256 || env_q >= 2)) {
         constexpr int env_qtarget = 256;
         const int rg = cdiv(a.ntaps * (a.KC / 4), 4);
         const int rgw = rg <= 4 ? 1 : rg <= 8 ? 2 : 3;
         a.nblocks = 1;
         a.DP = a.CoutP = 4 * kQBlocks;
-        const size_t bytes = 16 + (size_t)a.KP * 4 + (size_t)a.KP * a.DP * 4 + (((size_t)a.imgs * a.PR * a.PC * a.CP + 3) & ~(size_t)3) * 4 +
-                             (size_t)xf_groups * Cin * 8 + (xf_groups ? 16 : 0);
-        p->lds_bytes = bytes;
+        p->lds_bytes = qbytes;
         a.mblocks_per_chunk = cdiv(a.Mchunk, 64);   // slab rows as the 16x16x4 form with MTW = 1 (the reduction reads this format)
         a.Mrows_total = a.mblocks_per_chunk * 64;
         const int qby = cdiv(rg, 4 * rgw);

@@ -157,8 +157,8 @@ KNOWN_ENV = frozenset("""
 OCL_ASER_AUTOGRAD OCL_ASER_PIPELINE OCL_ASER_SPLIT OCL_BNB_EPI OCL_BN_CHAN OCL_BN_FUSED OCL_CBRS_EMULATE OCL_CBRS_VERIFY_EVERY
 OCL_CONV_PIPE OCL_CONV_Q4 OCL_CONV_S OCL_CONV_S_NT OCL_CONV_W OCL_CONV_WX OCL_DATA_STREAM OCL_DEBUG_SKIP_BN2FWD OCL_DEBUG_SKIP_SHORTCUT
 OCL_DEBUG_SKIP_WGRAD OCL_DETERMINISTIC OCL_DIST_BACKEND OCL_DY_KEEP OCL_GC_FREEZE OCL_GRAPH OCL_GRAPH_VERBOSE OCL_LIB OCL_LOG_PLANS
-OCL_PIN OCL_SIDE_EXTRA_MIN OCL_SINGLE_STREAM OCL_WGRAD_ENOUGH OCL_WGRAD_FLUSH OCL_WGRAD_MULTI OCL_WGRAD_MULTI_TARGET OCL_WGRAD_Q
-OCL_WGRAD_TARGET""".split())
+OCL_PIN OCL_SIDE_EXTRA_MIN OCL_SINGLE_STREAM OCL_WGRAD_ENOUGH OCL_WGRAD_FLUSH OCL_WGRAD_FLUSH_TAIL OCL_WGRAD_MULTI OCL_WGRAD_MULTI_TARGET
+OCL_WGRAD_Q OCL_WGRAD_TARGET""".split())
 HARNESS_ENV = frozenset("OCL_NONE OCL_TEST_CASES OCL_TEST_PORT OCL_SHARD_BACKEND OCL_PROBE_STREAM OCL_EAGER_DEVICE OCL_PARITY_REPORT".split())
 
 

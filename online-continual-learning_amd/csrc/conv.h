@@ -1,4 +1,5 @@
-// Internal interface of the conv / batch-norm kernels (conv.hip) used by the network engine (net.hip).
+// Internal interface of the conv / batch-norm kernels (planners and launch: conv.hip; kernels: conv_t*.hip, conv_q.hip, conv_s.hip, convw.hip,
+// wgrad.hip, bn.hip, conv_aux.hip) used by the network engine (net.hip).
 // Activations are NHWC fp32 with C in {4,20,40,80,160}; weights are re-packed per call from the
 // PyTorch OIHW master copy.  Everything is exact fp32 (v_mfma_f32_16x16x4_f32).
 #pragma once
@@ -174,12 +175,18 @@ void geom_fwd(const ConvShape& c, int N, int groups, ConvGeomDesc* g);
 // groups > 1: the tiles follow the BatchNorm groups of the pass (no tile straddles two groups: the EPI_BNB epilogue sums per group)
 void geom_dgrad(const ConvShape& c, int N, std::vector<ConvGeomDesc>* out, bool merge_classes = false, int groups = 1);
 int launch_conv(const ConvPlan& p, hipStream_t s);
+// the kernel instantiation for a plan's form, nullptr: none (each selector lives with its kernel family; launch_conv and conv_kernels_init call them)
+typedef void (*conv_fn_t)(const ConvArgs);
+conv_fn_t convt_plain_fn(int MT, int NT, int PF, int res, int cls, int pipe);   // conv_t.hip: conv_t_kernel without the EPI_BNB epilogue
+conv_fn_t convt_bnb_fn(int MT, int NT, int PF, int res, int cls, int pipe);     // conv_t_bnb.hip: conv_t_kernel with it
+conv_fn_t convq_fn(int ntq, int pf, int stats);         // conv_q.hip; stats: 0 none, 1 EPI_STATS, 2 EPI_BNB
+conv_fn_t convq_trace_fn(int ntq, int pf, int stats);   // conv_q.hip: the measurement builds
+conv_fn_t convs_fn(int nt, bool trace = false, bool bnb = false, bool det = false);   // conv_s.hip
 // conv_w_kernel (convw.hip): its planner (OCL_ERR_ARG: the geometry does not fit the form), its tables, its launch, its per-device set-up
 int plan_conv_w(const ConvGeomDesc& g, ConvPlan* p);
 void conv_w_tables(const ConvPlan& p, std::vector<int>* out);
 int launch_conv_w(const ConvPlan& p, hipStream_t s);
 int convw_kernels_init();
-int convw_set_det(int on);   // this translation unit's copy of the batch-sum mode flag (conv_stats_dev.h)
 
 // ---- wgrad -------------------------------------------------------------------------------------------
 struct WgradArgs {
@@ -399,5 +406,8 @@ int conv_kernels_init();
 int wgrad_kernels_init();   // wgrad.hip; called by conv_kernels_init
 // batch sums as order-independent integers (1) or fp64 atomics (0, default): see StatCell.  Synchronises the device.
 int set_deterministic_sums(int on);
+// the setters of the translation units' copies of the mode flag: each unit that includes conv_stats_dev.h appends its own at load time
+typedef hipError_t (*det_flag_setter_t)(int);
+std::vector<det_flag_setter_t>& det_flag_setters();
 
 }  // namespace ocl

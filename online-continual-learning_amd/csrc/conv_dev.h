@@ -1,5 +1,6 @@
-// Device-side helpers and constants shared by the translation units of the convolution engine (conv.hip: forward / data gradient /
-// BatchNorm kernels; wgrad.hip: weight gradient).  Header-only: everything here is inline / constexpr.
+// Device-side helpers and constants shared by the translation units of the convolution engine (conv.hip: planners and launch; conv_t*.hip,
+// conv_q.hip, conv_s.hip, convw.hip: forward / data gradient; bn.hip: BatchNorm; wgrad.hip: weight gradient).  Header-only: everything here
+// is inline / constexpr.
 #pragma once
 #include "conv.h"
 
@@ -8,6 +9,22 @@ namespace ocl {
 static const size_t kLdsLimit = 160 * 1024;      // hardware: 160 KiB per workgroup
 static const size_t kLdsTarget = 72 * 1024;      // weight-gradient planner target (2 workgroups per CU)
 constexpr int kQBlocks = 5;   // blocks of four output channels (Cout <= 20)
+
+// ---- constants the planners (conv.hip) and the kernels they plan for must agree on
+// conv_t_kernel (conv_t_kernel.h)
+constexpr int kWPF = 4;                        // float4 weight-prefetch registers per thread (staged weights)
+constexpr size_t kResidentBytes = 80 * 1024;   // weights of one channel split kept in LDS for the workgroup's lifetime up to this
+constexpr int kMaxWgTiles = 64;                // tile descriptors a workgroup keeps in LDS
+// PIPE variant of its staged-weight path: stage geometry by MT: QS groups with 256 * WPF == QS * 16 * MT units (every thread commits WPF whole
+// units) and an even number of rounds per stage (the two operand register sets then alternate the same way in every stage).
+#ifndef OCL_RING_SPREAD
+#define OCL_RING_SPREAD 1
+#endif
+__host__ __device__ constexpr int pipe_qs(int MT) { return MT == 1 ? 64 : MT == 2 ? 32 : 16; }
+__host__ __device__ constexpr int pipe_wpf(int MT) { return pipe_qs(MT) * 16 * MT / 256; }
+// conv_s_kernel (conv_s.hip)
+constexpr int kDepthS = 4;    // weight rounds in flight per wave
+constexpr int kPFS = 7;       // patch units (16 bytes) per lane and staging pass: a wave stages 448 units per pass (layer 4 needs 360 - 405; 8 would spill at 96 VGPRs)
 
 // =====================================================================================================
 // helpers shared by the convolution and the weight-gradient kernels

@@ -1,7 +1,7 @@
-// Device-side batch-sum / BatchNorm helpers shared by the translation units that accumulate or read BatchNorm statistics (conv.hip:
-// conv_t / conv_q / conv_s kernels and the BatchNorm kernels; convw.hip: conv_w_kernel).  Header-only.  Without relocatable device code every
-// translation unit that includes this file owns a copy of the __constant__ mode flag g_det_sums: set_deterministic_sums (conv.hip) sets its own
-// copy and calls the other units' setters (convw_set_det).
+// Device-side batch-sum / BatchNorm helpers shared by the translation units that accumulate or read BatchNorm statistics (conv_t.hip,
+// conv_t_bnb.hip, conv_q.hip, conv_s.hip, convw.hip: the convolution kernels; bn.hip: the BatchNorm kernels).  Header-only.  Without relocatable
+// device code every translation unit that includes this file owns a copy of the __constant__ mode flag g_det_sums and registers a setter for
+// it (below); set_deterministic_sums (conv.hip) calls them all.
 #pragma once
 #include "conv_dev.h"
 
@@ -15,6 +15,15 @@ namespace ocl {
 //    two atomics per partial sum instead of one: +12 % on the SCR step, +13 % on ER (profiles/r4_batch_sums_ab.txt) -- which is why
 //    it is a mode and not the default.
 static __constant__ int g_det_sums = 0;
+// A unit's copy stays a run-time value only while host code of that unit names HIP_SYMBOL(g_det_sums): without such a reference nothing can
+// write it, the compiler folds it to 0 and the deterministic branches vanish without a warning.  So every unit that includes this header
+// registers, when the library is loaded, a setter for its own copy (det_flag_setters, conv.hip), and no per-file setter is kept by hand.
+namespace {   // (one type per unit: its constructor names this unit's setter)
+hipError_t det_flag_set_here(int v) { return hipMemcpyToSymbol(HIP_SYMBOL(g_det_sums), &v, sizeof(int)); }
+const struct DetFlagUnit {
+    DetFlagUnit() { det_flag_setters().push_back(det_flag_set_here); }
+} g_det_flag_unit;
+}  // namespace
 // MODE -1: read the flag at run time; 0 / 1: compiled for the default / deterministic mode only (conv_s_kernel: a 96-register kernel
 // that cannot carry both paths without spilling -- its two instantiations are chosen by the host's copy of the flag)
 template <int MODE>

@@ -955,12 +955,6 @@ static convw_fn_t convwx_fn(int MT, int NT, int NR, int NU, int bnb, int xf, int
     return nullptr;
 }
 
-int convw_set_det(int on) {
-    const int v = on ? 1 : 0;
-    OCL_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_det_sums), &v, sizeof(int)));
-    return OCL_OK;
-}
-
 int convw_kernels_init() {
     for (int m = 1; m <= 3; ++m)
         for (int n = 1; n <= 2; ++n)

@@ -1,5 +1,5 @@
 // K3: weight gradient of the Reduced-ResNet18 convolutions for gfx950 (its own translation unit: the kernel has ~90 instantiations and
-// compiles beside conv.hip instead of behind it).
+// compiles beside the convolution kernels' units (conv_t.hip, conv_t_bnb.hip, ...) instead of behind them).
 //
 //  conv_wgrad_kernel  weight gradient as a (tap,ci) x co GEMM reduced over pixels, split-K over pixel tiles,
 //                     partials summed by wgrad_reduce_kernel straight into PyTorch's OIHW gradient.

@@ -1,5 +1,6 @@
 """Per-kernel register / LDS / occupancy table of a HIP source (hipcc -Rpass-analysis=kernel-resource-usage), one line per kernel.
-   python scripts/kernel_resources.py online-continual-learning_amd/csrc/conv.hip [filter]"""
+   python scripts/kernel_resources.py online-continual-learning_amd/csrc/conv_t.hip [filter]
+   (one translation unit per call: conv_t.hip, conv_t_bnb.hip, conv_q.hip, conv_s.hip, convw.hip, wgrad.hip, bn.hip, ...)"""
 import re
 import subprocess
 import sys

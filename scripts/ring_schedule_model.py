@@ -1,4 +1,4 @@
-"""Index model of conv_t_kernel's three-buffer weight ring (csrc/conv.hip, template parameter PIPE; OCL_CONV_PIPE=1).
+"""Index model of conv_t_kernel's three-buffer weight ring (csrc/conv_t_kernel.h, template parameter PIPE; OCL_CONV_PIPE=1).
 
 Replays, for random plans (classes, groups per class, chunks, tiles per workgroup, groups per stage), the control flow of one wave of
 `seq` (whole stages as one loop body: first round pair with the stage's bookkeeping, then plain pairs; a partial last stage with its

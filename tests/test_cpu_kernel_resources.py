@@ -1,6 +1,6 @@
 """CPU: the hot kernels must not use scratch (a private segment is paid at wave launch: profiles/r3_conv_s_ab.md -- a conv_s_kernel build
-with 10 spilled VGPRs was 1 - 4 us per launch slower than the build before it, with a faster loop).  Compiles conv.hip, wgrad.hip and convw.hip for
-gfx950 with the compiler's resource remarks (no GPU needed; the two files side by side) and reads ScratchSize per kernel."""
+with 10 spilled VGPRs was 1 - 4 us per launch slower than the build before it, with a faster loop).  Compiles every translation unit that
+holds one of them for gfx950 with the compiler's resource remarks (no GPU needed; the files side by side) and reads ScratchSize per kernel."""
 import re
 import shutil
 import subprocess
@@ -10,7 +10,7 @@ import pytest
 from conftest import ROOT
 
 HIPCC = "/opt/rocm/bin/hipcc"
-SRCS = [ROOT + "/online-continual-learning_amd/csrc/" + f for f in ("conv.hip", "wgrad.hip", "convw.hip")]
+SRCS = [ROOT + "/online-continual-learning_amd/csrc/" + f for f in ("conv_t.hip", "conv_t_bnb.hip", "conv_q.hip", "conv_s.hip", "bn.hip", "wgrad.hip", "convw.hip")]
 
 # the kernels a training / eval step launches (templates: the instantiations the planner picks at the BASELINE sizes)
 HOT = [

@@ -1,4 +1,4 @@
-"""CPU: the convolution / weight-gradient planner (host code of csrc/conv.hip and csrc/wgrad.hip) through `kbench ... plan`, which needs no GPU.
+"""CPU: the convolution / weight-gradient planner (host code of csrc/conv.hip, which holds no kernel, and of csrc/wgrad.hip) through `kbench ... plan`, which needs no GPU.
 
 Every layer of Reduced-ResNet18 at the batch sizes the path uses (replay-sized, the SCR step's 220 views, the 410-image eval-mode
 pass, mini-ImageNet's 84x84) must get a tiling that fits the LDS; the experimental three-buffer weight ring (OCL_CONV_PIPE=1,
@@ -14,7 +14,7 @@ from conftest import ROOT
 CSRC = os.path.join(ROOT, "online-continual-learning_amd", "csrc")
 KBENCH = os.path.join(CSRC, "kbench")
 LDS_LIMIT = 160 * 1024
-PIPE_QS = {1: 64, 2: 32, 3: 16, 4: 16, 5: 16}      # conv.hip: pipe_qs(MT)
+PIPE_QS = {1: 64, 2: 32, 3: 16, 4: 16, 5: 16}      # conv_dev.h: pipe_qs(MT)
 
 
 def _plan_lines(n, groups, hw, env=None):

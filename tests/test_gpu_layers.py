@@ -812,6 +812,46 @@ def test_deterministic_cells_at_their_limits(lib):
         lib.ocl_set_deterministic(0)
 
 
+@pytest.mark.parametrize("one_pass,want", [(1, 2031), (0, 3001)])   # bn_bwd_fused_kernel<3, 1>; bn_bwd_reduce_kernel + bn_bwd_apply_kernel
+def test_deterministic_flag_reaches_the_bn_backward_kernels(lib, one_pass, want):
+    """The BatchNorm backward writes and reads its batch sums inside its own translation unit, so no host-side decoding of the cells can
+    tell which mode its kernels ran in: a mode flag that never reaches that unit gives right answers in the wrong mode.  The range limit does
+    tell: channel 0's gradient is 2^47 at every pixel (exact in fp32; a single element is above the 7e13 limit of a fixed-point partial sum),
+    so the default mode sums it exactly (1024 * 2^47 = 2^57) and the deterministic mode must poison that channel's cells (NaN)."""
+    from ocl_amd import ffi
+    n, hw, c, groups = 4, 16, 40, 1
+    g = torch.Generator().manual_seed(29)
+    dz = ints((n, hw, hw, c), g)
+    dz[..., 0] = 2.0 ** 47
+    zm = torch.ones((n, hw, hw, c), dtype=torch.float64)
+    y, gamma, beta = _bn_case(g, n, hw, c, groups)
+    _, mean, invstd, _ = _bn_ref(y, groups, gamma, beta)
+    dy, dgm, dbt = (t[..., 1:].numpy() for t in _bn_bwd_ref(dz, zm, y, groups, gamma))
+    try:
+        for det in (0, 1):
+            lib.ocl_set_deterministic(det)
+            a = ffi.TestBnBwdArgs(m_per_group=n * hw * hw, groups=groups, c=c, nsets=1, one_pass=one_pass)
+            keep = [dev(dz.float()), dev(zm.float())]
+            a.dz, a.z = p(keep[0]), p(keep[1])
+            ts = [dev(t.float()) for t in (y, mean, invstd, gamma, beta)] + [dev(torch.full(y.shape, float("nan"))), dev(torch.zeros(c)), dev(torch.zeros(c))]
+            for f, t in zip(("y", "mean", "invstd", "gamma", "beta", "dy", "dgamma", "dbeta"), ts):
+                getattr(a, f)[0] = t.data_ptr()
+            path = lib.ocl_test_bn_bwd(C.byref(a), None)
+            assert path == want, (path, want, lib.ocl_last_error())
+            got_dy, got_dgm, got_dbt = (t.double().cpu().numpy() for t in ts[5:])
+            if det:
+                assert np.isnan(got_dbt[0]) and np.isnan(got_dgm[0]), (got_dbt[0], got_dgm[0])
+            else:
+                assert got_dbt[0] == n * hw * hw * 2.0 ** 47, got_dbt[0]
+                assert np.isfinite(got_dy).all() and np.isfinite(got_dgm).all() and np.isfinite(got_dbt).all()
+            # channels 1 - 39 are ordinary in both modes
+            np.testing.assert_allclose(got_dy[..., 1:], dy, rtol=1e-4, atol=2e-5 * float(np.abs(dy).max()))
+            np.testing.assert_allclose(got_dgm[1:], dgm, rtol=1e-4, atol=1e-4 * float(np.abs(dgm).max()))
+            np.testing.assert_allclose(got_dbt[1:], dbt, rtol=1e-4, atol=1e-4 * float(np.abs(dbt).max()))
+    finally:
+        lib.ocl_set_deterministic(0)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # forms reachable only through a switch read once per process: each set in a fresh child interpreter (never os.exec*)
 # ---------------------------------------------------------------------------------------------------------------------------------

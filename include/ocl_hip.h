@@ -85,6 +85,21 @@ int ocl_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
                   float beta1, float beta2, float eps, float weight_decay, float grad_scale, int64_t step,
                   int64_t skip_begin, int64_t skip_end, void* stream);
 
+/* ---- K8c: A-GEM gradient projection ----------------------------------------------------------------
+ * agents/agem.py:72-80 on the flat gradient array, between backward and the optimiser step:
+ *   prod = sum g*g_ref;  prod_ref = sum g_ref*g_ref;
+ *   out = prod < 0 ? g - (prod / prod_ref) * g_ref : g        (out is written over g_ref_inout)
+ * Two launches on `stream`, no host synchronisation, no atomics.  Products and sums are formed in double in a
+ * fixed order (block count a function of n alone): two runs give the same bits.  prod < 0 is false for NaN and
+ * for g_ref == 0; a not-projected output is a bit copy of g.  coef = (float)(prod / prod_ref).  info4 (may be
+ * NULL) receives {(float)prod, (float)prod_ref, projected ? coef : 0, projected ? 1 : 0}.
+ * `workspace`: at least ocl_agem_workspace_doubles(n) doubles of device memory, 8-byte aligned (the per-block
+ * partial pairs; at most 1024).  g and g_ref_inout 16-byte aligned and disjoint; OCL_ERR_ARG before any launch
+ * for a null or misaligned pointer, n <= 0, overlapping arrays or a workspace that is too small. */
+int64_t ocl_agem_workspace_doubles(int64_t n);
+int ocl_agem_project(const float* g, float* g_ref_inout, int64_t n, double* workspace,
+                     int64_t workspace_doubles, float* info4, void* stream);
+
 /* ---- K6: softmax cross-entropy ---------------------------------------------------------------------
  * torch.nn.CrossEntropyLoss(reduction='mean') (agents/base.py:95,113) and
  * F.cross_entropy(reduction='none') (utils/buffer/mir_retrieve.py:26-27).

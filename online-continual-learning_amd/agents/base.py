@@ -151,6 +151,17 @@ class ContinualLearner(torch.nn.Module, metaclass=abc.ABCMeta):
                     p.grad.data.mul_(scale)
             self.opt.step()
 
+    def _kd_mix(self, loss, logits, x):
+        """CE blended with the distillation loss against last task's model (exp_replay.py:42-47 / :64-69, agem.py:41-46)."""
+        trick = self.params.trick
+        if trick['kd_trick']:
+            w = 1 / (self.task_seen + 1)
+            loss = w * loss + (1 - w) * self.kd_manager.get_kd_loss(logits, x)
+        if trick['kd_trick_star']:
+            w = 1 / ((self.task_seen + 1) ** 0.5)
+            loss = w * loss + (1 - w) * self.kd_manager.get_kd_loss(logits, x)
+        return loss
+
     def _host_labels(self, labels):
         h = getattr(labels, 'host', None)
         return np.asarray(h).astype(np.int64) if h is not None else labels.detach().cpu().numpy().astype(np.int64)

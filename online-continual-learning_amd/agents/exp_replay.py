@@ -32,17 +32,6 @@ class ExperienceReplay(ContinualLearner):
         self.mem_iters = params.mem_iters
 
     # ---- pieces of a step ----------------------------------------------------------------------------------------------
-    def _kd_mix(self, loss, logits, x):
-        """CE blended with the distillation loss against last task's model (exp_replay.py:42-47 / :64-69)."""
-        trick = self.params.trick
-        if trick['kd_trick']:
-            w = 1 / (self.task_seen + 1)
-            loss = w * loss + (1 - w) * self.kd_manager.get_kd_loss(logits, x)
-        if trick['kd_trick_star']:
-            w = 1 / ((self.task_seen + 1) ** 0.5)
-            loss = w * loss + (1 - w) * self.kd_manager.get_kd_loss(logits, x)
-        return loss
-
     def _track(self, meters, logits, labels, loss):
         """Running loss / accuracy (only when printing: the reference's per-iteration .item() would stall the stream)."""
         if not self.verbose:

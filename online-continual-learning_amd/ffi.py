@@ -95,6 +95,8 @@ SIGNATURES = {
     "ocl_gather_u8_hwc_to_f32_chw": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp]),
     "ocl_sgd_step": (C.c_int, [vp, vp, i64, f32, f32, f32, vp, vp]),
     "ocl_adam_step": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, i64, i64, i64, vp]),
+    "ocl_agem_workspace_doubles": (i64, [i64]),
+    "ocl_agem_project": (C.c_int, [vp, vp, i64, vp, i64, vp, vp]),
     "ocl_ce_fwd_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "ocl_ce_segmented_fwd_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     "ocl_kd_fwd_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]),

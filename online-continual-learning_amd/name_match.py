@@ -31,6 +31,21 @@ agents = _Lazy({
     'SCR': ('.agents.scr', 'SupContrastReplay'),
 })
 
+# agents beyond the BASELINE hot path (`agents` keeps the keys INTEGRATION.md section 1 moves; these are added by name, section 1b)
+extra_agents = _Lazy({
+    'AGEM': ('.agents.agem', 'AGEM'),
+})
+
+
+def get_agent(key):
+    """The agent class registered under `key`: `agents` first, then `extra_agents`; KeyError otherwise."""
+    if key in agents:
+        return agents[key]
+    if key in extra_agents:
+        return extra_agents[key]
+    raise KeyError(key)
+
+
 retrieve_methods = _Lazy({
     'MIR': ('.plugins.mir_retrieve', 'MIR_retrieve'),
     'random': ('.plugins.random_retrieve', 'Random_retrieve'),

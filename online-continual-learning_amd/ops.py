@@ -154,6 +154,33 @@ def adam_step(params_flat, grads_flat, exp_avg, exp_avg_sq, step, lr, betas=(0.9
     return params_flat
 
 
+# ---- K8c ---------------------------------------------------------------------------------------------
+_agem_workspaces = {}
+
+
+def agem_project(g, g_ref_inout, workspace=None, info=None):
+    """A-GEM's projection (agents/agem.py:72-80) in two launches: g_ref_inout <- g - (g.g_ref / g_ref.g_ref) * g_ref where g.g_ref < 0,
+    else a copy of g; returns g_ref_inout.  workspace: a float64 tensor of ocl_agem_workspace_doubles(n) elements (default: one per
+    (device, n), allocated once); info: a float32 tensor of 4 that receives prod, prod_ref, the coefficient and the decision."""
+    ffi.init()
+    n = g.numel()
+    if (g.dtype != torch.float32 or g_ref_inout.dtype != torch.float32 or g_ref_inout.numel() != n or not g.is_cuda
+            or g.device != g_ref_inout.device):
+        raise RuntimeError("agem_project: two float32 arrays of one length on one GPU")
+    if workspace is None:
+        key = (g.device.index, n)
+        workspace = _agem_workspaces.get(key)
+        if workspace is None:
+            workspace = _agem_workspaces[key] = torch.empty(ffi.lib().ocl_agem_workspace_doubles(n), dtype=torch.float64, device=g.device)
+    elif workspace.dtype != torch.float64 or workspace.device != g.device:
+        raise RuntimeError("agem_project: the workspace is a float64 tensor on the gradients' device")
+    if info is not None and (info.dtype != torch.float32 or info.numel() < 4 or info.device != g.device):
+        raise RuntimeError("agem_project: info is a float32 tensor of 4 on the gradients' device")
+    ffi.check(ffi.lib().ocl_agem_project(ffi.ptr(g), ffi.ptr(g_ref_inout), n, ffi.ptr(workspace), workspace.numel(), ffi.ptr(info),
+                                         ffi.stream()), "agem_project")
+    return g_ref_inout
+
+
 # ---- K6 ----------------------------------------------------------------------------------------------
 def cross_entropy(logits, y, reduction="mean", want_grad=True, dl_out=None):
     """(loss, dlogits): torch.nn.CrossEntropyLoss / F.cross_entropy(reduction='none').  dl_out: a contiguous float32 [n, c] tensor

@@ -22,7 +22,7 @@ def single_run(params, tasks, tests, seed):
     model = setup_architecture(params)
     model = maybe_cuda(model, params.cuda)
     opt = setup_opt(params.optimizer, model, params.learning_rate, params.weight_decay)
-    agent = name_match.agents[params.agent](model, opt, params)
+    agent = name_match.get_agent(params.agent)(model, opt, params)
     test_loaders = setup_test_loader(tests, params)
     tmp_acc = []
     eval_s = []

@@ -100,6 +100,35 @@ int64_t ocl_agem_workspace_doubles(int64_t n);
 int ocl_agem_project(const float* g, float* g_ref_inout, int64_t n, double* workspace,
                      int64_t workspace_doubles, float* info4, void* stream);
 
+/* ---- K8d: EWC++ bookkeeping -------------------------------------------------------------------------
+ * agents/ewc_pp.py on flat arrays of n floats, all 16-byte aligned and pairwise disjoint; no host
+ * synchronisation, no atomics; OCL_ERR_ARG ("ewc: ...") before any launch for a null or misaligned pointer,
+ * n <= 0, overlapping arrays or a workspace that is too small.
+ *
+ * ocl_ewc_accumulate (:83-92, :104-106), once per step between backward and the optimiser step, one launch:
+ *   d = p - p_prev;  g' = g + scale * f_hat * d;  tmp += g' * g'       (g' over g, the sum over tmp)
+ * scale = 2 * lambda * w, w the weight the KD tricks put on the loss (1 without them).  prev_params and
+ * fisher_hat both NULL (first task): tmp += g * g alone, g is not written.  scale == 0 does not write g either.
+ * One of the two NULL is an argument error.  With penalty_out != NULL every block also writes a double partial
+ * of sum f_hat * d * d (d formed in double) to `workspace` (at least ocl_ewc_workspace_doubles(n) doubles, at
+ * most 512, 8-byte aligned) and a second one-block launch adds them in index order: penalty_out[0] = (float)sum
+ * (0 without prev_params).  With penalty_out == NULL the workspace is neither needed nor touched.
+ *
+ * ocl_ewc_fisher_ema (:97-102), one launch: running = keep * running + gain * tmp with both products and the
+ * sum rounded separately (no fma: the bits of the float32 statement), then tmp = 0.
+ *
+ * ocl_ewc_fisher_normalize (:76-80), two launches: fisher_hat = (running - min) / (max - min + 1e-32f) in IEEE
+ * float32, min and max over the whole array; a NaN anywhere makes min, max and every output NaN.  `workspace`:
+ * 2 * ocl_ewc_workspace_doubles(n) floats (the same workspace serves both calls).  minmax_out2 (may be NULL)
+ * receives {min, max}. */
+int64_t ocl_ewc_workspace_doubles(int64_t n);
+int ocl_ewc_accumulate(float* grads_inout, float* tmp_fisher_inout, const float* params, const float* prev_params,
+                       const float* fisher_hat, int64_t n, float scale, double* workspace, int64_t workspace_doubles,
+                       float* penalty_out, void* stream);
+int ocl_ewc_fisher_ema(float* running_inout, float* tmp_inout, int64_t n, float keep, float gain, void* stream);
+int ocl_ewc_fisher_normalize(const float* running, float* fisher_hat_out, int64_t n, float* workspace,
+                             int64_t workspace_floats, float* minmax_out2, void* stream);
+
 /* ---- K6: softmax cross-entropy ---------------------------------------------------------------------
  * torch.nn.CrossEntropyLoss(reduction='mean') (agents/base.py:95,113) and
  * F.cross_entropy(reduction='none') (utils/buffer/mir_retrieve.py:26-27).

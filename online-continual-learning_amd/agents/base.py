@@ -162,6 +162,17 @@ class ContinualLearner(torch.nn.Module, metaclass=abc.ABCMeta):
             loss = w * loss + (1 - w) * self.kd_manager.get_kd_loss(logits, x)
         return loss
 
+    def _kd_weight(self):
+        """The factor _kd_mix puts on the loss it is given (1 without the KD tricks): what a term of that loss whose gradient is formed
+        outside autograd has to carry (ewc_pp.py:45-51 blend the whole total_loss, penalty included)."""
+        trick = self.params.trick
+        w = 1.0
+        if trick['kd_trick']:
+            w *= 1 / (self.task_seen + 1)
+        if trick['kd_trick_star']:
+            w *= 1 / ((self.task_seen + 1) ** 0.5)
+        return w
+
     def _host_labels(self, labels):
         h = getattr(labels, 'host', None)
         return np.asarray(h).astype(np.int64) if h is not None else labels.detach().cpu().numpy().astype(np.int64)

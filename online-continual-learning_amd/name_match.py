@@ -37,12 +37,17 @@ extra_agents = _Lazy({
 })
 
 
+# regularisation-based agents: no replay memory, their bookkeeping runs on the flat parameter and gradient arrays (section 1b as well)
+regularization_agents = _Lazy({
+    'EWC': ('.agents.ewc_pp', 'EWC_pp'),
+})
+
+
 def get_agent(key):
-    """The agent class registered under `key`: `agents` first, then `extra_agents`; KeyError otherwise."""
-    if key in agents:
-        return agents[key]
-    if key in extra_agents:
-        return extra_agents[key]
+    """The agent class registered under `key`: `agents` first, then `extra_agents`, then `regularization_agents`; KeyError otherwise."""
+    for table in (agents, extra_agents, regularization_agents):
+        if key in table:
+            return table[key]
     raise KeyError(key)
 
 

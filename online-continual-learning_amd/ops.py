@@ -181,6 +181,73 @@ def agem_project(g, g_ref_inout, workspace=None, info=None):
     return g_ref_inout
 
 
+# ---- K8d ---------------------------------------------------------------------------------------------
+_ewc_workspaces = {}
+
+
+def _ewc_check(what, first, *rest):
+    n = first.numel()
+    for t in (first,) + rest:
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_cuda or t.device != first.device):
+            raise RuntimeError("%s: float32 arrays of one length on one GPU" % what)
+    return n
+
+
+def _ewc_workspace(what, first, n, workspace):
+    if workspace is None:
+        key = (first.device.index, n)
+        workspace = _ewc_workspaces.get(key)
+        if workspace is None:
+            workspace = _ewc_workspaces[key] = torch.empty(ffi.lib().ocl_ewc_workspace_doubles(n), dtype=torch.float64, device=first.device)
+    elif workspace.dtype != torch.float64 or workspace.device != first.device:
+        raise RuntimeError("%s: the workspace is a float64 tensor on the arrays' device" % what)
+    return workspace
+
+
+def ewc_accumulate(grads_inout, tmp_fisher_inout, params, prev_params=None, fisher_hat=None, scale=0.0, workspace=None, penalty_out=None):
+    """EWC++'s per-step bookkeeping (agents/ewc_pp.py:83-92, :104-106) in one launch: grads += scale * fisher_hat * (params - prev_params),
+    tmp_fisher += grads ** 2; with prev_params and fisher_hat both None (first task) only the second.  penalty_out: a float32 tensor
+    of 1 that receives sum fisher_hat * (params - prev_params) ** 2 (a second, one-block launch; the float64 workspace of
+    ocl_ewc_workspace_doubles(n) elements is used only then -- default: one per (device, n), allocated once).  Returns grads_inout."""
+    ffi.init()
+    if (prev_params is None) != (fisher_hat is None):
+        raise RuntimeError("ewc_accumulate: prev_params and fisher_hat are given together or not at all")
+    n = _ewc_check("ewc_accumulate", grads_inout, tmp_fisher_inout, params, prev_params, fisher_hat)
+    if penalty_out is not None:
+        if penalty_out.dtype != torch.float32 or penalty_out.numel() < 1 or penalty_out.device != grads_inout.device:
+            raise RuntimeError("ewc_accumulate: penalty_out is a float32 tensor of 1 on the arrays' device")
+        workspace = _ewc_workspace("ewc_accumulate", grads_inout, n, workspace)
+    elif workspace is not None and (workspace.dtype != torch.float64 or workspace.device != grads_inout.device):
+        raise RuntimeError("ewc_accumulate: the workspace is a float64 tensor on the arrays' device")
+    ffi.check(ffi.lib().ocl_ewc_accumulate(ffi.ptr(grads_inout), ffi.ptr(tmp_fisher_inout), ffi.ptr(params), ffi.ptr(prev_params),
+                                           ffi.ptr(fisher_hat), n, float(scale), ffi.ptr(workspace),
+                                           0 if workspace is None else workspace.numel(), ffi.ptr(penalty_out), ffi.stream()),
+              "ewc_accumulate")
+    return grads_inout
+
+
+def ewc_fisher_ema(running_inout, tmp_inout, keep, gain):
+    """running = keep * running + gain * tmp in float32 with separately rounded products (agents/ewc_pp.py:97-100), then tmp = 0 (:102)."""
+    ffi.init()
+    n = _ewc_check("ewc_fisher_ema", running_inout, tmp_inout)
+    ffi.check(ffi.lib().ocl_ewc_fisher_ema(ffi.ptr(running_inout), ffi.ptr(tmp_inout), n, float(keep), float(gain), ffi.stream()),
+              "ewc_fisher_ema")
+    return running_inout
+
+
+def ewc_fisher_normalize(running, fisher_hat_out, workspace=None, minmax_out=None):
+    """fisher_hat_out = (running - min) / (max - min + 1e-32) over the whole array in IEEE float32 (agents/ewc_pp.py:76-80), two
+    launches; minmax_out: a float32 tensor of 2 that receives min and max.  Returns fisher_hat_out."""
+    ffi.init()
+    n = _ewc_check("ewc_fisher_normalize", running, fisher_hat_out)
+    workspace = _ewc_workspace("ewc_fisher_normalize", running, n, workspace)
+    if minmax_out is not None and (minmax_out.dtype != torch.float32 or minmax_out.numel() < 2 or minmax_out.device != running.device):
+        raise RuntimeError("ewc_fisher_normalize: minmax_out is a float32 tensor of 2 on the arrays' device")
+    ffi.check(ffi.lib().ocl_ewc_fisher_normalize(ffi.ptr(running), ffi.ptr(fisher_hat_out), n, ffi.ptr(workspace), 2 * workspace.numel(),
+                                                 ffi.ptr(minmax_out), ffi.stream()), "ewc_fisher_normalize")
+    return fisher_hat_out
+
+
 # ---- K6 ----------------------------------------------------------------------------------------------
 def cross_entropy(logits, y, reduction="mean", want_grad=True, dl_out=None):
     """(loss, dlogits): torch.nn.CrossEntropyLoss / F.cross_entropy(reduction='none').  dl_out: a contiguous float32 [n, c] tensor

@@ -129,6 +129,23 @@ int ocl_ewc_fisher_ema(float* running_inout, float* tmp_inout, int64_t n, float 
 int ocl_ewc_fisher_normalize(const float* running, float* fisher_hat_out, int64_t n, float* workspace,
                              int64_t workspace_floats, float* minmax_out2, void* stream);
 
+/* ---- K8e: global L2-norm gradient clip ---------------------------------------------------------------
+ * torch.nn.utils.clip_grad_norm_ (norm_type 2, error_if_nonfinite off; agents/gdumb.py:82) on the flat gradient
+ * array, between backward and the optimiser step:
+ *   total = sqrt(sum g*g);  coef = max_norm / (total + 1e-6);  g *= min(coef, 1)
+ * Two launches on `stream`, no host synchronisation, no atomics.  Squares and sums are formed in double in a
+ * fixed order (block count a function of n alone): two runs give the same bits.  sqrt and the IEEE divide are
+ * done in double, coef = (float)(that quotient).  Where the quotient is >= 1 (or rounds to 1.0f) no element is
+ * read or written; otherwise every element becomes g * coef, one rounded float multiply.  A NaN norm multiplies
+ * through (every element NaN); an infinite norm gives coef = 0 (finite elements 0, infinite ones NaN).  info4
+ * (may be NULL) receives {(float)total, clipped ? coef : 1, clipped ? 1 : 0, (float)sum g*g}.
+ * `workspace`: at least ocl_clip_workspace_doubles(n) doubles of device memory, 8-byte aligned (the per-block
+ * partials; at most 512).  grads_inout 16-byte aligned; OCL_ERR_ARG ("clip: ...") before any launch for a null
+ * or misaligned pointer, n <= 0, max_norm negative or NaN, or a workspace that is too small. */
+int64_t ocl_clip_workspace_doubles(int64_t n);
+int ocl_clip_grad_norm(float* grads_inout, int64_t n, float max_norm, double* workspace, int64_t workspace_doubles,
+                       float* info4, void* stream);
+
 /* ---- K6: softmax cross-entropy ---------------------------------------------------------------------
  * torch.nn.CrossEntropyLoss(reduction='mean') (agents/base.py:95,113) and
  * F.cross_entropy(reduction='none') (utils/buffer/mir_retrieve.py:26-27).

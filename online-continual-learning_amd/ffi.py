@@ -101,6 +101,8 @@ SIGNATURES = {
     "ocl_ewc_accumulate": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, vp, i64, vp, vp]),
     "ocl_ewc_fisher_ema": (C.c_int, [vp, vp, i64, f32, f32, vp]),
     "ocl_ewc_fisher_normalize": (C.c_int, [vp, vp, i64, vp, i64, vp, vp]),
+    "ocl_clip_workspace_doubles": (i64, [i64]),
+    "ocl_clip_grad_norm": (C.c_int, [vp, i64, f32, vp, i64, vp, vp]),
     "ocl_ce_fwd_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "ocl_ce_segmented_fwd_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     "ocl_kd_fwd_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]),

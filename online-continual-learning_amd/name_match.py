@@ -43,9 +43,16 @@ regularization_agents = _Lazy({
 })
 
 
+# agents that train offline on their memory at every task's end (section 1b as well)
+offline_agents = _Lazy({
+    'GDUMB': ('.agents.gdumb', 'Gdumb'),
+})
+
+
 def get_agent(key):
-    """The agent class registered under `key`: `agents` first, then `extra_agents`, then `regularization_agents`; KeyError otherwise."""
-    for table in (agents, extra_agents, regularization_agents):
+    """The agent class registered under `key`: `agents` first, then `extra_agents`, `regularization_agents` and `offline_agents`;
+    KeyError otherwise."""
+    for table in (agents, extra_agents, regularization_agents, offline_agents):
         if key in table:
             return table[key]
     raise KeyError(key)

@@ -181,6 +181,40 @@ def agem_project(g, g_ref_inout, workspace=None, info=None):
     return g_ref_inout
 
 
+# ---- K8e ---------------------------------------------------------------------------------------------
+_clip_workspaces = {}
+_clip_infos = {}
+
+
+def clip_grad_norm_(grads_flat, max_norm, workspace=None, info=None):
+    """torch.nn.utils.clip_grad_norm_ (norm_type 2, error_if_nonfinite off) on a flat gradient array, in two launches and in place:
+    total = sqrt(sum g * g), g *= min(max_norm / (total + 1e-6), 1).  Returns the total norm as a one-element device tensor (a view of
+    info[0]; no synchronisation), as torch's function does.  workspace: a float64 tensor of ocl_clip_workspace_doubles(n) elements
+    (default: one per (device, n), allocated once); info: a float32 tensor of at least 4 that receives the total norm, the coefficient
+    (1.0 when nothing was clipped), the decision and sum g * g (default: one per device, allocated once)."""
+    ffi.init()
+    n = grads_flat.numel()
+    if grads_flat.dtype != torch.float32 or not grads_flat.is_cuda or not grads_flat.is_contiguous():
+        raise RuntimeError("clip_grad_norm_: a contiguous float32 array on the GPU")
+    dev = grads_flat.device
+    if workspace is None:
+        key = (dev.index, n)
+        workspace = _clip_workspaces.get(key)
+        if workspace is None:
+            workspace = _clip_workspaces[key] = torch.empty(ffi.lib().ocl_clip_workspace_doubles(n), dtype=torch.float64, device=dev)
+    elif workspace.dtype != torch.float64 or workspace.device != dev:
+        raise RuntimeError("clip_grad_norm_: the workspace is a float64 tensor on the gradients' device")
+    if info is None:
+        info = _clip_infos.get(dev.index)
+        if info is None:
+            info = _clip_infos[dev.index] = torch.zeros(4, dtype=torch.float32, device=dev)
+    elif info.dtype != torch.float32 or info.numel() < 4 or info.device != dev or not info.is_contiguous():
+        raise RuntimeError("clip_grad_norm_: info is a float32 tensor of at least 4 on the gradients' device")
+    ffi.check(ffi.lib().ocl_clip_grad_norm(ffi.ptr(grads_flat), n, float(max_norm), ffi.ptr(workspace), workspace.numel(), ffi.ptr(info),
+                                           ffi.stream()), "clip_grad_norm")
+    return info.reshape(-1)[0:1]
+
+
 # ---- K8d ---------------------------------------------------------------------------------------------
 _ewc_workspaces = {}
 

@@ -232,7 +232,22 @@ int ocl_cosine_max(const float* mem, int k, int64_t n, const float* g, float eps
  * the per-sample parameters are drawn on the host and passed in.  params: n rows of
  * OCL_AUG_NPARAM floats: [y0,x0,crop_h,crop_w (input pixels, fractional), flip(0/1),
  * jitter_on(0/1), brightness, contrast, saturation, hue (fraction of a turn), order (0..23 index
- * of the permutation of the four jitter ops), gray(0/1)]. x, out: [n,3,h,w] fp32 in [0,1]. */
+ * of the permutation of the four jitter ops), gray(0/1)]. x, out: [n,3,h,w] fp32 in [0,1].
+ * Given the parameters the result is fully determined (tests/augment_ref.py states it in float64).  Output pixel (oy, ox), in order:
+ *   1. flip: the column read is ox' = w - 1 - ox if flip, else ox (the flip comes BEFORE the source coordinate: the crop box keeps
+ *      its place in the input, its content is mirrored);
+ *   2. crop + resize, half-pixel centres: sy = y0 + (oy + 0.5) * crop_h / h - 0.5, sx = x0 + (ox' + 0.5) * crop_w / w - 0.5, each
+ *      clamped to the IMAGE, [0, h - 1] and [0, w - 1] (not to the crop box: near the box's edge the neighbours outside it are
+ *      read), then bilinear between floor(s) and min(floor(s) + 1, size - 1), per channel;
+ *   3. if jitter_on: the four operations 0 brightness, 1 contrast, 2 saturation, 3 hue in the order given by `order`, the index
+ *      into the 24 permutations of (0, 1, 2, 3) in lexicographic order (0: 0123, 1: 0132, ... 23: 3210).  brightness:
+ *      clamp01(c + (brightness - 1)); contrast: clamp01(c * contrast); saturation: to HSV, s = clamp01(s * saturation), back;
+ *      hue: to HSV, h = h + hue (a fraction of a turn, any real number), back.  HSV is the usual hexcone: v = max, s = (max - min) /
+ *      max (0 for black), h in [0, 1) from the channel that is the maximum (r first, then g, on ties), 0 for a gray; the way back
+ *      takes the fractional part of h;
+ *   4. if gray: all three channels become 0.299 r + 0.587 g + 0.114 b.
+ * n <= 65535 (one grid row per image) and h * w <= 2^31 - 256 (pixel indices are int): anything larger is refused with OCL_ERR_ARG
+ * before a launch. */
 #define OCL_AUG_NPARAM 12
 int ocl_scr_augment(const float* x, float* out, int n, int h, int w, const float* params,
                     void* stream);
@@ -469,12 +484,15 @@ int ocl_test_net_forms(int hw, int nf, int n, int groups, int train, ocl_test_ne
  *   ARGSORT     n
  *   NCM_MEANS   d, n_cls             NCM_PREDICT: n, d, n_cls
  *   GEMM        m, n, k
+ *   AUGMENT     n, h, w              (ocl_scr_augment, and the image launch of ocl_scr_augment_uniform)
+ *   AUG_PARAMS  n                    (the parameter launch of ocl_scr_augment_uniform)
  * Returns the OCL_PATH_* code (> 0) and fills *plan (may be NULL); 0 for an unknown op or a wrong argument count.  A *_REFUSED code
  * means the entry point returns OCL_ERR_ARG on the host before any launch. */
 enum {
     OCL_SOP_ROWS = 0, OCL_SOP_PAIR = 1, OCL_SOP_U8 = 2, OCL_SOP_SGD = 3, OCL_SOP_COSINE = 4, OCL_SOP_CE = 5, OCL_SOP_CE_SEG = 6,
     OCL_SOP_KD = 7, OCL_SOP_MIR = 8, OCL_SOP_SUPCON = 9, OCL_SOP_KNN = 10, OCL_SOP_COL_REDUCE = 11, OCL_SOP_ASER = 12,
-    OCL_SOP_ARGSORT = 13, OCL_SOP_NCM_MEANS = 14, OCL_SOP_NCM_PREDICT = 15, OCL_SOP_GEMM = 16
+    OCL_SOP_ARGSORT = 13, OCL_SOP_NCM_MEANS = 14, OCL_SOP_NCM_PREDICT = 15, OCL_SOP_GEMM = 16,
+    OCL_SOP_AUGMENT = 17, OCL_SOP_AUG_PARAMS = 18
 };
 enum {
     OCL_PATH_ROWS_COPY16 = 1,          /* 16-byte units (row_bytes % 16 == 0, src and dst 16-byte aligned), grid.y < 8 */
@@ -521,7 +539,10 @@ enum {
     OCL_PATH_NCM_PREDICT = 42,
     OCL_PATH_GEMM_K16 = 43,            /* k % 16 == 0: the unrolled loop only */
     OCL_PATH_GEMM_KTAIL = 44,          /* k < 16: the 4-wide tail loop only */
-    OCL_PATH_GEMM_KBOTH = 45
+    OCL_PATH_GEMM_KBOTH = 45,
+    OCL_PATH_AUGMENT = 46,             /* augment_kernel: ceil(h w / 256) x n workgroups of 256, one thread per output pixel */
+    OCL_PATH_AUGMENT_REFUSED = 47,     /* n > 65535 (grid.y) or h w > 2^31 - 256 (int pixel index) */
+    OCL_PATH_AUG_PARAMS = 48           /* aug_params_kernel: ceil(n / 64) workgroups of 64, one thread per image */
 };
 typedef struct {
     int32_t path;                      /* OCL_PATH_* */

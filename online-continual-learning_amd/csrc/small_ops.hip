@@ -105,6 +105,14 @@ static SPlan plan_ncm_predict(int n, int d, int n_cls) { return splan(OCL_PATH_N
 static SPlan plan_gemm(int m, int n, int k) {
     return splan(k % 16 == 0 ? OCL_PATH_GEMM_K16 : k < 16 ? OCL_PATH_GEMM_KTAIL : OCL_PATH_GEMM_KBOTH, (unsigned)cdiv(n, 16), (unsigned)cdiv(m, 16), 64);
 }
+// augment_kernel: one thread per output pixel, one grid row per image.  grid.y cannot exceed 65535, and the kernel forms the pixel
+// index (up to the last workgroup's end) and h * w in int: larger sizes are refused here, before a launch.  n = 0: no launch.
+static SPlan plan_augment(int64_t n, int64_t h, int64_t w) {
+    if (n > 65535 || h * w > (int64_t)0x7fffffff - 255) return splan(OCL_PATH_AUGMENT_REFUSED);
+    if (n == 0) return splan(OCL_PATH_AUGMENT);
+    return splan(OCL_PATH_AUGMENT, (unsigned)((h * w + 255) / 256), (unsigned)n, 256);
+}
+static SPlan plan_aug_params(int64_t n) { return splan(OCL_PATH_AUG_PARAMS, (unsigned)((n + 63) / 64), 1, 64); }
 
 // =====================================================================================================
 // K9 gather / scatter of replay-buffer rows
@@ -1247,11 +1255,13 @@ int ocl_ncm_predict(const float* feat, int n, int d, const float* means, int n_c
 
 int ocl_scr_augment(const float* x, float* out, int n, int h, int w, const float* params, void* stream) {
     OCL_REQUIRE(n >= 0 && h > 0 && w > 0, "augment: bad shape");
+    const SPlan pl = plan_augment(n, h, w);
+    OCL_REQUIRE(pl.path != OCL_PATH_AUGMENT_REFUSED, "augment: n=%d h=%d w=%d too large (n <= 65535, h*w <= 2^31-256)", n, h, w);
     if (n == 0) return OCL_OK;
     OCL_REQUIRE(x && out && params && x != out, "augment: null pointer or in-place");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_BN, s);
-    hipLaunchKernelGGL(augment_kernel, dim3(cdiv(h * w, 256), n), dim3(256), 0, s, x, out, h, w, params);
+    hipLaunchKernelGGL(augment_kernel, dim3(pl.grid_x, pl.grid_y), dim3(pl.block), 0, s, x, out, h, w, params);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -1259,6 +1269,8 @@ int ocl_scr_augment(const float* x, float* out, int n, int h, int w, const float
 int ocl_scr_augment_uniform(const float* x, float* out, int n, int h, int w, const float* u, const double* cfg12, float* params,
                             void* stream) {
     OCL_REQUIRE(n >= 0 && h > 0 && w > 0, "augment: bad shape");
+    const SPlan pl = plan_augment(n, h, w), pp = plan_aug_params(n);
+    OCL_REQUIRE(pl.path != OCL_PATH_AUGMENT_REFUSED, "augment: n=%d h=%d w=%d too large (n <= 65535, h*w <= 2^31-256)", n, h, w);
     if (n == 0) return OCL_OK;
     OCL_REQUIRE(x && out && u && cfg12 && params && x != out, "augment: null pointer or in-place");
     AugCfg cfg;
@@ -1276,9 +1288,9 @@ int ocl_scr_augment_uniform(const float* x, float* out, int n, int h, int w, con
     cfg.j1[3] = (float)(2.0 * cfg12[7]);
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_BN, s);
-    hipLaunchKernelGGL(aug_params_kernel, dim3(cdiv(n, 64)), dim3(64), 0, s, u, n, h, w, cfg, params);
+    hipLaunchKernelGGL(aug_params_kernel, dim3(pp.grid_x), dim3(pp.block), 0, s, u, n, h, w, cfg, params);
     OCL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(augment_kernel, dim3(cdiv(h * w, 256), n), dim3(256), 0, s, x, out, h, w, (const float*)params);
+    hipLaunchKernelGGL(augment_kernel, dim3(pl.grid_x, pl.grid_y), dim3(pl.block), 0, s, x, out, h, w, (const float*)params);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }
@@ -1296,7 +1308,7 @@ int ocl_gemm_small(const float* a, int64_t a_rs, int64_t a_cs, const float* b, i
 }
 
 int ocl_test_small_op_path(int op, const int64_t* a, int na, ocl_small_op_plan* plan) {
-    static const int kArgs[] = {4, 5, 4, 4, 4, 3, 2, 2, 2, 5, 5, 2, 1, 1, 2, 3, 3};
+    static const int kArgs[] = {4, 5, 4, 4, 4, 3, 2, 2, 2, 5, 5, 2, 1, 1, 2, 3, 3, 3, 1};
     const int n_ops = (int)(sizeof(kArgs) / sizeof(kArgs[0]));
     if (op < 0 || op >= n_ops || !a || na != kArgs[op]) {
         ocl::set_error("small_op_path: op %d takes %d arguments, got %d", op, op >= 0 && op < n_ops ? kArgs[op] : -1, na);
@@ -1321,7 +1333,9 @@ int ocl_test_small_op_path(int op, const int64_t* a, int na, ocl_small_op_plan* 
         case OCL_SOP_ARGSORT: p = plan_argsort((int)a[0]); break;
         case OCL_SOP_NCM_MEANS: p = plan_ncm_means((int)a[0], (int)a[1]); break;
         case OCL_SOP_NCM_PREDICT: p = plan_ncm_predict((int)a[0], (int)a[1], (int)a[2]); break;
-        default: p = plan_gemm((int)a[0], (int)a[1], (int)a[2]); break;
+        case OCL_SOP_GEMM: p = plan_gemm((int)a[0], (int)a[1], (int)a[2]); break;
+        case OCL_SOP_AUGMENT: p = plan_augment(a[0], a[1], a[2]); break;
+        default: p = plan_aug_params(a[0]); break;
     }
     if (plan) *plan = p;
     return p.path;

@@ -1,5 +1,5 @@
 """The parity cases of the small kernels (csrc/small_ops.hip: gather / scatter, SGD, cosine-max, cross-entropy and its relatives, SupCon,
-kNN-Shapley, column reductions, argsort, NCM, the small MFMA GEMM), shared by tests/test_cpu_small_ops.py (every kernel and every path
+kNN-Shapley, column reductions, argsort, NCM, the small MFMA GEMM, the SCR augmentation), shared by tests/test_cpu_small_ops.py (every kernel and every path
 code of ocl_test_small_op_path is claimed by a case that still reaches it; no GPU) and tests/test_gpu_small_ops.py (runs every case).
 
 Plain data.  A case is a dict:
@@ -32,9 +32,12 @@ OPS = {
     "ncm_means": (14, ["ncm_means_kernel"]),
     "ncm_predict": (15, ["ncm_predict_kernel"]),
     "gemm": (16, ["gemm_small_kernel"]),
+    "augment": (17, ["augment_kernel"]),
+    "aug_params": (18, ["aug_params_kernel"]),
 }
-# parity of the augmentation kernels is unpinned by design; their property tests are in test_gpu_kernels.py
-EXEMPT_KERNELS = ["augment_kernel", "aug_params_kernel"]
+# no kernel of the file is exempt.  (kornia's random DRAWS stay unpinned; what the two augmentation kernels do with
+# given draws / parameters is their own contract, include/ocl_hip.h K13, stated in float64 by tests/augment_ref.py)
+EXEMPT_KERNELS = []
 
 
 def _c(name, key, path, seed, **kw):
@@ -171,9 +174,40 @@ GEMM = [_c("%s_m%d_n%d_k%d" % (fname, m, n, k), "gemm:%s k%%16=%d" % ({"dw": "a_
            _gemm_path(k), 210 + fi * 8 + ki, m=m, n=n, k=k, **form)
         for fi, (fname, form) in enumerate(_G_FORMS) for ki, (k, (m, n)) in enumerate(zip(_G_K, _G_MN[fi:] + _G_MN[:fi]))]
 
+# ---- SCR augmentation, image kernel: n images of h x w (one thread per pixel, workgroups of 256: 5x7 is under one, 17x23 = 391 and
+# 84x84 = 7056 end in a partial one); kind: how tests/augment_ref.py::augment_case_inputs builds pixels and parameters; off = (x, params,
+# out); extra: rows allocated past n (sentinels: the kernel must leave them alone) ----------------------------------------------------------
+AUGMENT = [
+    _c("orders_same_image", "augment:orders one image in the 24 orders augment:partial_block 17x23", "AUGMENT", 301, n=24, h=17, w=23, kind="orders_same"),
+    # (a contrast of 0.75 never clamps and so commutes with saturation and hue: 8 distinct images.  1.4 clamps: 18, all the contract allows)
+    _c("orders_same_image_clamped", "augment:orders one image in the 24 orders, contrast 1.4 reaches the clamp", "AUGMENT", 317, n=24, h=17, w=23,
+       kind="orders_same", contrast=1.4),
+    _c("orders_mixed","augment:orders one per image, random crops and factors", "AUGMENT", 302, n=24, h=32, w=32, kind="orders_mixed"),
+    _c("hsv_sectors", "augment:hsv_sectors branches, ties, sectors; hue shifts and saturation factors", "AUGMENT", 303, n=10, h=5, w=7, kind="hsv"),
+    _c("clamps", "augment:clamps brightness / contrast at 0 and 1", "AUGMENT", 304, n=4, h=5, w=7, kind="clamps"),
+] + [_c("geometry_%dx%d" % (h, w), "augment:fractional_crop augment:geometry %dx%d corners, 1x1, tall, wide, flip%s" % (h, w, " augment:partial_block" if h * w % 256 else ""),
+        "AUGMENT", 305 + i, n=20, h=h, w=w, kind="geometry") for i, (h, w) in enumerate([(5, 7), (17, 23), (32, 32), (84, 84)])] + [
+    _c("gray", "augment:gray alone and after jitter, h != w", "AUGMENT", 310, n=3, h=17, w=23, kind="gray"),
+    _c("n1", "augment:n=1", "AUGMENT", 311, n=1, h=5, w=7, kind="random"),
+    _c("n0", "augment:n0", "AUGMENT", 312, n=0, h=5, w=7, kind="random", extra=1),
+    _c("misaligned", "augment:misaligned x, params, out", "AUGMENT", 313, n=5, h=17, w=23, kind="random", off=(1, 3, 1)),
+    _c("guard", "augment:guard rows past n untouched", "AUGMENT", 314, n=3, h=17, w=23, kind="random", extra=2),
+    _c("refuse_n", "augment:refuse grid.y", "AUGMENT_REFUSED", 315, n=65536, h=1, w=1, kind="refuse"),
+    _c("refuse_hw", "augment:refuse int pixel index", "AUGMENT_REFUSED", 316, n=1, h=46341, w=46341, kind="refuse"),
+]
+# ---- SCR augmentation, parameter kernel: n rows of 30 draws (one thread per row, workgroups of 64), image size h x w, crop scale range;
+# every case's parameter buffer has sentinel rows past n.  (16, 64) and (64, 16) with scale (0.99, 1): no attempt fits, the two fallback
+# crops with the clamped aspect ratio.  The seeds are chosen so that at most 1 % of a case's rows have a rounding decision on a boundary
+# (tests/test_cpu_small_ops.py asserts it, from the float64 reference alone) ---------------------------------------------------------------
+_AP_SIZES = [((32, 32), (0.2, 1.0)), ((84, 84), (0.2, 1.0)), ((16, 64), (0.99, 1.0)), ((64, 16), (0.99, 1.0))]
+AUG_PARAMS = [_c("%dx%d_n%d" % (h, w, n), "aug_params:%s %dx%d n=%d%s" % ("partial_block" if n % 64 else "full_blocks", h, w, n, " fallback crop" if h != w else ""),
+                 "AUG_PARAMS", 330 + 4 * i + j, n=n, h=h, w=w, scale=sc)
+              for i, ((h, w), sc) in enumerate(_AP_SIZES) for j, n in enumerate([1, 63, 65, 110])] + \
+             [_c("extremes", "aug_params:extremes draws of exactly 0 and 1 - 2^-24", "AUG_PARAMS", 350, n=256, h=32, w=32, scale=(0.2, 1.0), special="extremes")]
+
 CASES = {"rows": ROWS, "pair": PAIR, "u8": U8, "sgd": SGD, "cosine": COSINE, "ce": CE, "ce_seg": CE_SEG, "kd": KD, "mir": MIR, "supcon": SUPCON,
          "knn": KNN, "col_reduce": COL_REDUCE, "aser": ASER, "argsort": ARGSORT, "ncm_means": NCM_MEANS, "ncm_predict": NCM_PREDICT,
-         "gemm": GEMM}
+         "gemm": GEMM, "augment": AUGMENT, "aug_params": AUG_PARAMS}
 
 # the path keys the suite must keep (a case may be renamed, these substrings must stay claimed)
 REQUIRED_KEYS = [
@@ -183,7 +217,8 @@ REQUIRED_KEYS = [
     "sgd:refuse_misaligned", "gemm:a_transposed", "gemm:a_transposed+accumulate", "gemm:accumulate+relu", "gemm:c_rs>n", "knn:vec_both d4n=5",
     "knn:vec_both d4n=6", "knn:vec_both d4n=7", "knn:wave misaligned", "knn:k>=n_cand larger", "ncm_means: n=30 d=640", "ncm_predict: n=20 d=160 n_cls=10 ties=1",
     "col_reduce: rows=3 ", "col_reduce: rows=8 cols=64", "col_reduce: rows=16 cols=1", "col_reduce: rows=64 cols=2048", "argsort: n=2 zeros", "argsort: n=3 inf",
-    "argsort: n=64 nan",
+    "argsort: n=64 nan", "augment:orders", "augment:hsv_sectors", "augment:partial_block", "augment:fractional_crop", "augment:clamps", "augment:gray",
+    "augment:misaligned", "augment:guard", "augment:refuse", "aug_params:partial_block", "aug_params:extremes",
 ]
 
 
@@ -227,4 +262,8 @@ def plan_args(op, c, ptrs=None):
         return [c["n"], c["d"], c["n_cls"]]
     if op == "gemm":
         return [c["m"], c["n"], c["k"]]
+    if op == "augment":
+        return [c["n"], c["h"], c["w"]]
+    if op == "aug_params":
+        return [c["n"]]
     raise KeyError(op)

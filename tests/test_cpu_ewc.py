@@ -32,6 +32,11 @@ MB = 1 << 24
 ARRAYS = ("g", "t", "p", "q", "f")
 
 
+def _id_value(v):
+    """A case value for a pytest id: addresses as their offset from A (A itself differs from process to process, and an id must not)."""
+    return "A+0x%x" % (v - A) if v >= A else str(v)
+
+
 def _accumulate(**over):
     kw = dict(g=A, t=A + MB, p=A + 2 * MB, q=A + 3 * MB, f=A + 4 * MB, n=16, scale=2.0, ws=A + 5 * MB, ws_doubles=2, pen=A + 6 * MB)
     kw.update(over)
@@ -103,7 +108,7 @@ def test_accumulate_refuses_each_array_misaligned_or_overlapping_without_a_devic
     (_normalize, dict(r=A + 4)), (_normalize, dict(f=A + MB + 8)), (_normalize, dict(ws=A + 5 * MB + 2)), (_normalize, dict(f=A)),
     (_normalize, dict(f=A + 48)), (_normalize, dict(ws=A + 32)), (_normalize, dict(mm=A + 16)),
     (_normalize, dict(ws_floats=1)), (_normalize, dict(n=4096, ws_floats=7)), (_normalize, dict(n=1 << 22, ws_floats=1023)),
-], ids=lambda v: v.__name__ if callable(v) else ",".join("%s=%s" % kv for kv in v.items()))
+], ids=lambda v: v.__name__ if callable(v) else ",".join("%s=%s" % (k, _id_value(x)) for k, x in v.items()))
 def test_ema_and_normalize_refuse_bad_arguments_without_a_device(call, over):
     rc, msg = call(**over)
     assert rc == OCL_ERR_ARG, (rc, msg)

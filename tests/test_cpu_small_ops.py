@@ -4,7 +4,10 @@
   from) is claimed by a case of tests/small_op_cases.py, and every case still reaches the path it claims;
 * the GPU file parametrizes every case of the table, unsliced;
 * the float64 reference functions of the GPU file reproduce the reference project's own fp32 results stored in tests/golden/ (so the
-  references the kernels are judged against are themselves pinned)."""
+  references the kernels are judged against are themselves pinned);
+* the float64 statement of the SCR augmentation (tests/augment_ref.py) is pinned too -- its HSV pair to colorsys, its crop to bilinear
+  interpolation, identity parameters to the input -- its cases tell every observable mutant of it from the reference by 100 times their
+  tolerance, the 24 jitter orders apart wherever the contract does, and at most 1 % of a parameter case's rows sit on a rounding boundary."""
 import ctypes as C
 import os
 import re
@@ -12,6 +15,7 @@ import re
 import numpy as np
 import pytest
 
+import augment_ref as AR
 import small_op_cases as SC
 from conftest import ROOT, gold
 import ocl_amd  # noqa: F401
@@ -105,11 +109,20 @@ def test_plans_are_what_the_header_documents(lib):
     assert (p.grid_x, p.grid_y, p.block) == (10, 14, 64)
     p = plan("ncm_predict", n=9, d=640, n_cls=100)
     assert (p.grid_x, p.lds_bytes) == (9, (640 + 100 + 16) * 4)
+    p = plan("augment", n=20, h=84, w=84)                       # one thread per pixel in workgroups of 256, one grid row per image
+    assert (p.grid_x, p.grid_y, p.block, p.lds_bytes) == (28, 20, 256, 0)
+    p = plan("augment", n=65535, h=17, w=23)
+    assert (p.grid_x, p.grid_y) == (2, 65535)
+    assert plan("augment", n=65536, h=17, w=23).grid_x == 0 and plan("augment", n=1, h=46341, w=46341).grid_x == 0      # refused
+    p = plan("augment", n=1, h=46340, w=46340)                  # the largest square whose pixel indices fit an int
+    assert (p.grid_x, p.grid_y) == (-(-46340 * 46340 // 256), 1)
+    p = plan("aug_params", n=110)                               # one thread per image in workgroups of 64
+    assert (p.grid_x, p.grid_y, p.block) == (2, 1, 64)
 
 
 # the size of the table: a case that leaves it (or joins it) is a deliberate edit of this line too
 CASE_COUNTS = {"rows": 9, "pair": 7, "u8": 5, "sgd": 8, "cosine": 13, "ce": 18, "ce_seg": 7, "kd": 7, "mir": 7, "supcon": 16, "knn": 11,
-               "col_reduce": 7, "aser": 6, "argsort": 12, "ncm_means": 5, "ncm_predict": 7, "gemm": 56}
+               "col_reduce": 7, "aser": 6, "argsort": 12, "ncm_means": 5, "ncm_predict": 7, "gemm": 56, "augment": 16, "aug_params": 17}
 
 
 def test_no_case_left_the_table():
@@ -209,3 +222,184 @@ def test_float64_knn_order_and_brute_force_reproduce_the_reference_golden():
                     assert np.abs(bf - O.knn_shapley_bruteforce(d64[r], cy == ey[r], k)).max() <= 1e-12
                 checked += 1
     assert checked >= 5
+
+
+# ---- the SCR augmentation: the float64 statement of the K13 contract (tests/augment_ref.py) is pinned, and the cases tell a wrong kernel ----
+def _aug_cases(run_only=True):
+    return [c for c in SC.CASES["augment"] if not (run_only and (c["kind"] == "refuse" or c["n"] == 0))]
+
+
+def _aug_case(name):
+    return [c for c in SC.CASES["augment"] if c["name"] == name][0]
+
+
+def test_augment_reference_hsv_pair_is_colorsys():
+    """rgb2hsv / hsv2rgb of the reference against the standard library, on the hand-picked pixels of the hsv_sectors case (which cover the
+    three maximum-channel branches, the negative-hue wrap, the ties, gray, 0, 1) and, for the way back, at every hue shift of the case (which
+    together reach the six sectors)."""
+    import colorsys
+    px = AR.hsv_sector_pixels().astype(np.float64)
+    h, s, v = AR.rgb2hsv(px[:, 0], px[:, 1], px[:, 2])
+    assert ((h >= 0) & (h < 1)).all()
+    branches = set()
+    for i, (r, g, b) in enumerate(px):
+        assert np.abs(np.array(colorsys.rgb_to_hsv(r, g, b)) - np.array([h[i], s[i], v[i]])).max() <= 1e-12, (i, r, g, b)
+        mx = max(r, g, b)
+        branches.add("gray" if mx == min(r, g, b) else "r_wrap" if mx == r and g < b else "r" if mx == r else "g" if mx == g else "b")
+    assert branches == {"gray", "r", "r_wrap", "g", "b"}
+    sectors = set()
+    for d in AR.HUE_SHIFTS:
+        rgb = AR.hsv2rgb(h + d, s, v)
+        for i in range(len(px)):
+            hh = (h[i] + d) % 1.0
+            assert np.abs(np.array(colorsys.hsv_to_rgb(hh, s[i], v[i])) - np.array([rgb[0][i], rgb[1][i], rgb[2][i]])).max() <= 1e-12, (d, i)
+            if s[i] > 0 and v[i] > 0:
+                sectors.add(int(hh * 6.0) % 6)
+    assert sectors == set(range(6))
+
+
+def test_augment_reference_crop_is_bilinear_interpolation():
+    """The crop-and-resize of the reference against torch.nn.functional.interpolate(bilinear, align_corners=False) in float64, on integer
+    crops, in the interior (output pixels whose two source rows and columns lie inside the box: at the box's edge interpolate clamps to the
+    box, the contract to the image); flipped, against the mirrored interpolation."""
+    import torch
+    rng = np.random.default_rng(7)
+    for h, w, (y0, x0, ch, cw) in [(32, 32, (8, 4, 16, 16)), (17, 23, (3, 5, 9, 14)), (84, 84, (10, 20, 33, 57)), (5, 7, (1, 2, 3, 4)), (17, 23, (0, 0, 17, 23))]:
+        x = rng.random((1, 3, h, w))
+        want = torch.nn.functional.interpolate(torch.from_numpy(x[:, :, y0:y0 + ch, x0:x0 + cw]), size=(h, w), mode="bilinear", align_corners=False).numpy()
+        sy = (np.arange(h) + 0.5) * ch / h - 0.5
+        sx = (np.arange(w) + 0.5) * cw / w - 0.5
+        iy, ix = (sy >= 0) & (sy <= ch - 1), (sx >= 0) & (sx <= cw - 1)
+        assert iy.sum() >= h // 2 and ix.sum() >= w // 2
+        for flip in (0, 1):
+            p = np.array([[y0, x0, ch, cw, flip, 0, 1, 1, 1, 0, 0, 0]], dtype=np.float32)
+            got = AR.ref_augment(x, p, np.float64)
+            exp = want[:, :, :, ::-1] if flip else want
+            keep = ix[::-1] if flip else ix
+            assert np.abs(got[:, :, iy][:, :, :, keep] - exp[:, :, iy][:, :, :, keep]).max() <= 1e-12, (h, w, flip)
+
+
+def test_augment_reference_identity_and_flags_are_exact():
+    """Identity parameters return the input, flip alone the mirrored input, bit for bit, in float64 and in the float32 restatement; a
+    jitter of neutral factors is the identity to round-off in every order."""
+    rng = np.random.default_rng(8)
+    for h, w in [(5, 7), (17, 23), (84, 84)]:
+        x = rng.random((2, 3, h, w)).astype(np.float32)
+        ident = np.tile(np.array([0, 0, h, w, 0, 0, 1, 1, 1, 0, 0, 0], dtype=np.float32), (2, 1))
+        flip = ident.copy()
+        flip[:, 4] = 1
+        for T in (np.float64, np.float32):
+            assert np.array_equal(AR.ref_augment(x, ident, T), x.astype(T))
+            assert np.array_equal(AR.ref_augment(x, flip, T), x.astype(T)[:, :, :, ::-1])
+        for order in range(24):
+            neutral = ident.copy()
+            neutral[:, 5], neutral[:, 10] = 1, order
+            assert np.abs(AR.ref_augment(x, neutral, np.float64) - x).max() <= 1e-12, order
+
+
+# the case of the table that tells each mutant of tests/augment_ref.py from the reference (None: see the test)
+MUTANT_CAUGHT_BY = {
+    "order_decode_13": "orders_same_image", "hsv2rgb_sector3_qt": "hsv_sectors", "rgb2hsv_no_wrap": None, "clamp_to_crop": "geometry_5x7",
+    "flip_after_coordinate": "geometry_17x23", "gray_before_jitter": "gray",
+}
+
+
+@pytest.mark.parametrize("mutant", sorted(AR.MUTANTS))
+def test_augment_cases_catch_every_mutant(mutant):
+    """A kernel carrying one of these errors would miss the named case by more than 100 times its tolerance.
+
+    rgb2hsv_no_wrap is the exception, and not for want of a case: it is no error.  Without the wrap rgb2hsv returns a hue in (-1/6, 0) for
+    the pixels whose maximum is red and g < b -- one full turn below the right one (asserted here, and it is what the colorsys pin above
+    catches) -- and the only consumer of that hue, hsv2rgb, takes the fractional part first (it must: the hue shift may be any real
+    number).  The image is the same: on every case of the table the mutant is within 1e-12 of the reference (largest difference 1.8e-15,
+    orders_mixed), so no case can be asked to catch it, and `if (h < 0.f) h += 6.f` in the kernel is not observable through the entry point."""
+    assert set(MUTANT_CAUGHT_BY) == set(AR.MUTANTS)
+    name = MUTANT_CAUGHT_BY[mutant]
+    if name is None:
+        px = AR.hsv_sector_pixels().astype(np.float64)
+        h, _, _ = AR.rgb2hsv(px[:, 0], px[:, 1], px[:, 2])
+        hm, _, _ = AR.rgb2hsv(px[:, 0], px[:, 1], px[:, 2], wrap=False)
+        neg = (px[:, 0] >= px[:, 1]) & (px[:, 0] >= px[:, 2]) & (px[:, 1] < px[:, 2])
+        assert neg.sum() >= 5 and np.abs((h - hm)[neg] - 1.0).max() <= 1e-12 and np.array_equal(h[~neg], hm[~neg])
+        for c in _aug_cases():
+            x, P, r64, _, _ = AR.augment_case_reference(c)
+            assert np.abs(AR.ref_augment(x[:c["n"]], P[:c["n"]], np.float64, mutant=mutant) - r64).max() <= 1e-12, c["name"]
+        return
+    c = _aug_case(name)
+    x, P, r64, E, tol = AR.augment_case_reference(c)
+    d = float(np.abs(AR.ref_augment(x[:c["n"]], P[:c["n"]], np.float64, mutant=mutant) - r64).max())
+    print("%s: %s differs from the reference by %.3g on %s (tolerance %.3g)" % (mutant, AR.MUTANTS[mutant], d, name, tol))
+    assert d > 100 * tol, (mutant, name, d, tol)
+
+
+@pytest.mark.parametrize("name, classes", [("orders_same_image", 8), ("orders_same_image_clamped", 18)])
+def test_augment_orders_of_one_image_are_pairwise_distinct(name, classes):
+    """One image, identical parameters but the order index (brightness 1.3, saturation 1.35, hue 0.08; contrast 0.75, or 1.4).  Any two orders
+    give images further apart than 100 times the case's tolerance, so a decode that took one for the other would show -- except where the
+    contract itself gives two orders the same image, for every input (AR.same_image_orders: saturation and hue commute; a contrast <= 1
+    never clamps and commutes with both).  Those pairs are asserted equal (within 1e-12) rather than distinct: with contrast 0.75 the 24
+    orders are 8 distinct images (largest difference inside a class 6.7e-16), which is why the case has a twin whose contrast of 1.4
+    reaches the clamp: 18 distinct images, the most the contract allows (the 6 pairs left differ by exchanging saturation and hue where one
+    follows the other; a decode that confused those would compute the same thing for any parameters)."""
+    c = _aug_case(name)
+    x, P, r64, E, tol = AR.augment_case_reference(c)
+    assert c["n"] == 24 and np.array_equal(P[:, 10], np.arange(24)) and (np.delete(P, 10, axis=1) == np.delete(P, 10, axis=1)[0]).all() and (x == x[0]).all()
+    assert (c["h"] * c["w"]) % 256 != 0 and c["h"] * c["w"] > 256
+    assert [float(v) for v in P[0, 5:10]] == [float(np.float32(v)) for v in (1, 1.3, c.get("contrast", 0.75), 1.35, 0.08)]
+    cls = []                         # one representative per class of orders the contract cannot tell apart
+    closest, inside = np.inf, 0.0
+    for i in range(24):
+        if not any(AR.same_image_orders(i, j, P[0, 7]) for j in cls):
+            cls.append(i)
+        for j in range(i):
+            d = float(np.abs(r64[i] - r64[j]).max())
+            if AR.same_image_orders(i, j, P[0, 7]):
+                inside = max(inside, d)
+                assert d <= 1e-12, (i, j, d)
+            else:
+                closest = min(closest, d)
+                assert d > 100 * tol, "orders %d and %d are %.3g apart (tolerance %.3g)" % (i, j, d, tol)
+    assert len(cls) == classes
+    print("%s: %d distinct images; closest two %.3g apart, tolerance %.3g; largest difference inside a class %.3g" % (name, len(cls), closest, tol, inside))
+
+
+def test_augment_case_tolerances_are_what_float32_costs():
+    """The tolerance of every case is 4 E with E the float32 restatement's own distance from float64, floor 8 * 2^-24: between one and a few
+    dozen float32 roundings of a value in [0, 1] at these sizes -- never wide enough to hide a wrong pixel."""
+    for c in _aug_cases():
+        x, P, r64, E, tol = AR.augment_case_reference(c)
+        assert r64.shape == (c["n"], 3, c["h"], c["w"]) and r64.min() >= 0 and r64.max() <= 1
+        assert tol == max(4 * E, 8 * U) and E > 0 and tol < 1e-4, (c["name"], E)
+    geo = _aug_case("geometry_84x84")
+    assert (geo["h"] * geo["w"]) % 256 != 0
+    _, P, _, _, _ = AR.augment_case_reference(geo)
+    assert (P[:, :4] != np.floor(P[:, :4])).any(1).sum() >= 4 and P[:, 4].sum() == len(P) // 2            # fractional boxes; half flipped
+
+
+@pytest.mark.parametrize("name", SC.ids("aug_params"))
+def test_aug_params_reference_and_its_exclusions(name):
+    """ref_aug_params against the host statement (ScrAugment.params_from_uniform, torch fp32) on every row whose rounding decisions are all
+    further than 2^-18 relative from their boundaries: integers equal, jitter factors within 2 float32 spacings.  At most 1 % of a case's
+    rows are excluded (a condition on the seeds, met by the reference alone).  Every row's box lies inside the image."""
+    import torch
+    from ocl_amd.agents.scr import ScrAugment
+    c = [c for c in SC.CASES["aug_params"] if c["name"] == name][0]
+    cfg = AR.aug_params_config(c)
+    aug = ScrAugment((c["h"], c["w"]), scale=c["scale"])
+    assert [float(v) for v in aug.config()] == cfg
+    u = AR.aug_params_case_inputs(c)
+    assert u.shape == (c["n"], AR.NUNIFORM) and u.min() >= 0 and u.max() <= 1 - U
+    P, D = AR.ref_aug_params(u, cfg, c["h"], c["w"])
+    ok = AR.comparable(D)
+    assert (~ok).sum() <= 0.01 * c["n"], "%d of %d rows on a rounding boundary" % ((~ok).sum(), c["n"])
+    assert AR.box_inside_image(P, c["h"], c["w"]).all()
+    host = aug.params_from_uniform(torch.from_numpy(u)).numpy().astype(np.float64)
+    assert AR.box_inside_image(host, c["h"], c["w"]).all()
+    ints = [0, 1, 2, 3, 4, 5, 10, 11]
+    assert np.array_equal(host[ok][:, ints], P[ok][:, ints])
+    assert (np.abs(host[ok][:, 6:10] - P[ok][:, 6:10]) <= 2 * AR.factor_ulps(cfg)).all()
+    if c["h"] != c["w"]:                      # no attempt fits: the fallback crop, ratio clamped to 4/3 (wide) or 3/4 (tall)
+        assert (P[:, 2:4] == ([16, 21] if c["w"] > c["h"] else [21, 16])).all() and not np.isfinite(D[:, 60:62]).any()
+    if c.get("special") == "extremes":
+        assert (u[0] == 0).all() and (u[1] == np.float32(1 - U)).all() and (u[2, 20:] == 0).all() and (u[3, 20:] == np.float32(1 - U)).all()
+        assert ok[0] and ok[2] and P[0, 10] == 0 and P[3, 10] == 23 and P[2, 0] == 0 and P[3, 0] + P[3, 2] == c["h"]

@@ -1,5 +1,5 @@
-"""GPU: every kernel of csrc/small_ops.hip but the two augmentation kernels, path by path (tests/small_op_cases.py), against float64 references
-written here from the formulas include/ocl_hip.h cites -- independent of oracle/ (fp32) and of the library.
+"""GPU: every kernel of csrc/small_ops.hip, the two augmentation kernels included, path by path (tests/small_op_cases.py), against float64 references
+written here (the augmentation's: tests/augment_ref.py) from the formulas include/ocl_hip.h cites -- independent of oracle/ (fp32) and of the library.
 
 Tier 1 (bit-equal, data chosen so that fp32 is exact): gather / scatter / pair / u8 (any data), the small GEMM and the column reductions on small
 integers, SGD with power-of-two hyper-parameters, argsort order, kNN order and Shapley values on integer-valued features, NCM ties.
@@ -11,7 +11,8 @@ Tier 2 (random fp32, per-element error against float64):
     of magnitude.  On the shapes the golden tests bound by 1e-5 the bound is capped at 1e-5.
 Every tensor handed to the library sits between sentinel regions (guarded.Guarded); after each call the regions are intact and inputs unchanged.
 Each case asserts that the entry point takes the path the table names (ocl_test_small_op_path on the real pointers).  Refusals are only tested
-where the plan says the entry point returns before launching.  With OCL_PARITY_REPORT=<file> the tier-2 figures are written there."""
+where the plan says the entry point returns before launching.  With OCL_PARITY_REPORT=<file> the tier-2 figures are written there, and the
+augmentation's (per case: E, the tolerance, the device error) to augment_parity.txt next to it (profiles/augment_parity.txt)."""
 import ctypes as C
 import math
 import os
@@ -21,6 +22,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import augment_ref as AR
 import small_op_cases as SC
 from guarded import Guarded
 
@@ -29,6 +31,7 @@ pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
 PFX = "OCL" + "_PATH_"
 REPORT = []
+AUG_REPORT = []
 
 
 @pytest.fixture(scope="module")
@@ -47,6 +50,15 @@ def lib(cuda):
                 f.write("%-44s %-8s %12.4g %12s %12.4g %8.3f\n" % row)
             worst = max(REPORT, key=lambda r: r[5])
             f.write("# closest to its bound: %s %s (ratio %.3f)\n" % (worst[0], worst[1], worst[5]))
+    if path and AUG_REPORT:
+        with open(os.path.join(os.path.dirname(os.path.abspath(path)), "augment_parity.txt"), "w") as f:
+            f.write("# the SCR augmentation kernels against the float64 statement of their contract (tests/augment_ref.py, tests/test_gpu_small_ops.py)\n"
+                    "# augment/*: E = max |float32 restatement - float64| on the case's inputs, tolerance = max(4 E, 8 * 2^-24), device error = max |kernel - float64|\n"
+                    "# aug_params/*: E column = rows compared exactly (all rounding decisions > 2^-18 from a boundary), tolerance and error in float32 spacings\n"
+                    "#               of the jitter factors; the integer parameters of those rows are equal\n")
+            f.write("%-36s %-8s %5s %12s %12s %12s %8s\n" % ("case", "size", "n", "E", "tolerance", "device_err", "ratio"))
+            for case, size, n, E, tol, err in AUG_REPORT:
+                f.write("%-36s %-8s %5d %12.4g %12.4g %12.4g %8.3f\n" % (case, size, n, E, tol, err, err / tol))
 
 
 def vp(t):
@@ -894,8 +906,143 @@ def test_supcon_anchor_without_positive_is_nan_everywhere(lib):
         assert bool(nan.all()), "bsz %d: %d of %d gradient elements are finite" % (bsz, int((~nan).sum()), nan.numel())
 
 
+# ==========================================================================================================================================
+# SCR augmentation: the image kernel and the parameter kernel against the float64 statement of their contract (tests/augment_ref.py)
+# ==========================================================================================================================================
+def _off3(c):
+    return c["off"] if isinstance(c["off"], tuple) else (c["off"],) * 3
+
+
+def _augment_refused(lib, c):
+    """The plan refuses on the host: both entry points return an error before any launch, so the (small) sentinel-filled outputs stay
+    as they were; through ops the error is a RuntimeError."""
+    from ocl_amd import ffi, ops
+    n, h, w = c["n"], c["h"], c["w"]
+    real = n * h * w <= 1 << 20                      # the tensors can have the shape the call names (otherwise: one pixel; nothing is read)
+    rows, hh, ww = (n, h, w) if real else (1, 1, 1)
+    g = Guarded()
+    d_x = g.inp(np.zeros((rows, 3, hh, ww), dtype=np.float32), 0, "x")
+    d_p = g.inp(np.tile(np.array([0, 0, h, w, 0, 0, 1, 1, 1, 0, 0, 0], dtype=np.float32), (rows, 1)), 0, "params")
+    d_u = g.inp(np.zeros((rows, AR.NUNIFORM), dtype=np.float32), 0, "u")
+    d_o, d_par = g.out((rows, 3, hh, ww), torch.float32, 0, "out"), g.out((rows, AR.NPARAM), torch.float32, 0, "params out")
+    cfg = [0.2, 1.0, 0.75, 4.0 / 3.0, 0.4, 0.4, 0.4, 0.1, 0.8, 0.2, float(w), float(h)]
+    assert assert_path(lib, "augment", c).grid_x == 0
+    rc = lib.ocl_scr_augment(vp(d_x), vp(d_o), n, h, w, vp(d_p), stream())
+    assert rc != 0 and b"too large" in lib.ocl_last_error()
+    with pytest.raises(RuntimeError):
+        ffi.check(rc, "scr_augment")
+    rc = lib.ocl_scr_augment_uniform(vp(d_x), vp(d_o), n, h, w, vp(d_u), (C.c_double * 12)(*cfg), vp(d_par), stream())
+    assert rc != 0 and b"too large" in lib.ocl_last_error()
+    if real:
+        with pytest.raises(RuntimeError):
+            ops.scr_augment(d_x, d_p)
+        with pytest.raises(RuntimeError):
+            ops.scr_augment_uniform(d_x, d_u, cfg, out=d_o)
+    g.check(c["name"])
+    assert bool((d_o == Guarded.POISON).all()) and bool((d_par == Guarded.POISON).all())
+
+
+@case_of("augment")
+def test_scr_augment_against_float64(lib, name):
+    """ocl_scr_augment (and ops.scr_augment, bit-equal to it) against ref_augment in float64, every element, the edge ring included.
+    Tolerance: 4 E, E the distance of the float32 restatement from float64 on the case's own inputs, at least 8 * 2^-24
+    (augment_ref.augment_case_reference; nothing of it looks at the kernel).  Rows that only move pixels (full crop, no jitter, no gray) are
+    the input, or its mirror image, bit for bit.  Rows past n -- of x, params and out -- are left alone."""
+    from ocl_amd import ops
+    c = find("augment", name)
+    if c["path"] == "AUGMENT_REFUSED":
+        return _augment_refused(lib, c)
+    n, h, w = c["n"], c["h"], c["w"]
+    off = _off3(c)
+    x, P, r64, E, tol = AR.augment_case_reference(c)
+    g = Guarded()
+    d_x, d_p = g.inp(x, off[0], "x"), g.inp(P, off[1], "params")
+    d_o = g.out(x.shape, torch.float32, off[2], "out")
+    plan = assert_path(lib, "augment", c)
+    assert (plan.grid_x, plan.grid_y, plan.block) == ((-(-h * w // 256), n, 256) if n else (0, 0, 0))
+    ok(lib, lib.ocl_scr_augment(vp(d_x), vp(d_o), n, h, w, vp(d_p), stream()), name)
+    g.check(name)
+    got = d_o.cpu().numpy()
+    assert (got[n:] == Guarded.POISON).all(), "%s: output rows past n written" % name
+    if n == 0:
+        return
+    assert ops.scr_augment(d_x[:n], d_p[:n]).cpu().numpy().tobytes() == got[:n].tobytes()
+    got = got[:n]
+    assert np.isfinite(got).all() and got.min() >= 0 and got.max() <= 1
+    err = float(np.abs(got.astype(np.float64) - r64).max())
+    AUG_REPORT.append(("augment/" + name, "%dx%d" % (h, w), n, E, tol, err))
+    print("augment/%s: float32 restatement E %.4g, tolerance %.4g, device error %.4g" % (name, E, tol, err))
+    exact = 0
+    for i in range(n):
+        if AR.flags_only(P[i], h, w):
+            want = x[i][:, :, ::-1] if P[i, 4] > 0.5 else x[i]
+            assert got[i].tobytes() == np.ascontiguousarray(want).tobytes(), "%s: row %d (flags only) is not its input bit for bit" % (name, i)
+            exact += 1
+    if c["kind"] == "geometry":
+        assert exact == 2
+    i = np.unravel_index(int(np.abs(got.astype(np.float64) - r64).argmax()), got.shape)
+    assert err <= tol, "%s: error %.4g against float64 at image %d channel %d pixel (%d, %d) exceeds %.4g (float32 restatement: %.4g)" % ((name, err) + tuple(i) + (tol, E))
+
+
+@case_of("aug_params")
+def test_scr_augment_parameters_against_float64(lib, name):
+    """ocl_scr_augment_uniform's parameter kernel against ref_aug_params: on the rows whose rounding decisions are all further than 2^-18
+    relative (32 float32 ulp, far above what expf and sqrtf differ by) from a boundary the integers are equal and the jitter factors within 2
+    float32 spacings (augment_ref.factor_ulps); every row's box lies inside the image.  The fused call's image is ocl_scr_augment on the
+    parameters it returned, bit for bit; ops.scr_augment_uniform returns the same; the parameter rows past n are left alone."""
+    from ocl_amd import ops
+    c = find("aug_params", name)
+    n, h, w = c["n"], c["h"], c["w"]
+    cfg = AR.aug_params_config(c)
+    u = AR.aug_params_case_inputs(c)
+    x = np.random.default_rng(c["seed"] + 1000).random((n, 3, h, w)).astype(np.float32)
+    g = Guarded()
+    d_x, d_u = g.inp(x, 0, "x"), g.inp(u, 0, "u")
+    d_o, d_par = g.out(x.shape, torch.float32, 0, "out"), g.out((n + 3, AR.NPARAM), torch.float32, 0, "params")
+    plan = assert_path(lib, "aug_params", c)
+    assert (plan.grid_x, plan.block) == (-(-n // 64), 64)
+    ok(lib, lib.ocl_scr_augment_uniform(vp(d_x), vp(d_o), n, h, w, vp(d_u), (C.c_double * 12)(*cfg), vp(d_par), stream()), name)
+    g.check(name)
+    got = d_par.cpu().numpy().astype(np.float64)
+    assert (got[n:] == Guarded.POISON).all(), "%s: parameter rows past n written" % name
+    got = got[:n]
+    P, D = AR.ref_aug_params(u, cfg, h, w)
+    rows = AR.comparable(D)
+    assert (~rows).sum() <= 0.01 * n
+    inside = AR.box_inside_image(got, h, w)
+    assert inside.all(), "%s: rows %s: crop box outside the image, or a flag / order out of range" % (name, np.nonzero(~inside)[0][:8])
+    ints = [0, 1, 2, 3, 4, 5, 10, 11]
+    bad = np.nonzero((got[:, ints] != P[:, ints]).any(1) & rows)[0]
+    assert len(bad) == 0, "%s: rows %s differ from float64: %s, reference %s" % (name, bad[:8], got[bad[:3]], P[bad[:3]])
+    ferr = np.abs(got[rows][:, 6:10] - P[rows][:, 6:10]) / AR.factor_ulps(cfg)
+    AUG_REPORT.append(("aug_params/" + name, "%dx%d" % (h, w), n, int(rows.sum()), 2.0, float(ferr.max())))
+    print("aug_params/%s: %d of %d rows compared exactly, largest jitter-factor difference %.3g float32 spacings" % (name, rows.sum(), n, ferr.max()))
+    assert ferr.max() <= 2.0
+    assert torch.equal(ops.scr_augment(d_x, d_par[:n]), d_o), "%s: the fused call's image is not ocl_scr_augment on its own parameters" % name
+    out2, par2 = ops.scr_augment_uniform(d_x, d_u, cfg, want_params=True)
+    assert torch.equal(out2, d_o) and torch.equal(par2, d_par[:n])
+
+
+def test_scr_augment_pieces_equal_the_concatenated_call(lib):
+    """ScrAugment.apply_parts -- the call the agent makes: one draw, one launch pair per piece at its row offset into the draws (7 rows of
+    30 floats: not 16-byte aligned) -- against the single-tensor call on the concatenation under the same seed, bit for bit."""
+    from ocl_amd.agents.scr import ScrAugment
+    rng = np.random.default_rng(77)
+    a, b = (torch.from_numpy(rng.random((k, 3, 17, 23)).astype(np.float32)).cuda() for k in (7, 3))
+    empty = torch.empty((0, 3, 17, 23), dtype=torch.float32, device=a.device)
+    torch.manual_seed(3)
+    parts = ScrAugment((17, 23))((a, b, empty))
+    torch.manual_seed(3)
+    whole = ScrAugment((17, 23))(torch.cat((a, b)))
+    torch.cuda.synchronize()
+    assert parts.shape == whole.shape == (10, 3, 17, 23)
+    assert torch.equal(parts, whole)
+    assert not torch.equal(whole, torch.cat((a, b)))
+
+
 # the per-case tests of every op of the table (tests/test_cpu_small_ops.py checks their parametrisation against the table)
 CASE_TESTS = {
+    "augment": [test_scr_augment_against_float64], "aug_params": [test_scr_augment_parameters_against_float64],
     "rows": [test_gather_rows_is_exact, test_scatter_rows_is_exact_and_leaves_other_rows], "pair": [test_gather_pair_is_exact],
     "u8": [test_gather_u8_images_is_exact], "sgd": [test_sgd_is_exact_on_integers], "cosine": [test_cosine_max], "ce": [test_cross_entropy],
     "ce_seg": [test_cross_entropy_segmented], "kd": [test_kd_loss], "mir": [test_mir_scores], "supcon": [test_supcon],

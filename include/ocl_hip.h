@@ -345,9 +345,9 @@ int ocl_net_forward_segments(ocl_net* net, const float* const* xs, const int32_t
 int ocl_net_backward(ocl_net* net, int slot, const float* dout, int accumulate, void* stream);
 
 /* Test hooks. debug_stop: make ocl_net_backward return right after stage block*10+step (step 1: bn2 backward,
- * 2: conv2 data gradient, 3: bn1 backward, 4: conv1 data gradient, 5: block input gradient complete; 990: after the
- * head; -1: off).  debug_copy what: 0 raw conv output (NHWC) of conv `index`; 1 output of block `index`; 2 gradient
- * scratch buffer `index`; 3 gradient buffer by role (0..4 = gA..gE) at the last stop; 4 activation a1 of block `index`; 5 stem output. */
+ * 2: conv2 data gradient, 3: bn1 backward, 4: conv1 data gradient, 5: block input gradient complete; -1: off).
+ * debug_copy what: 0 raw conv output (NHWC) of conv `index`; 1 output of block `index`; 2 gradient scratch buffer
+ * `index`; 3 gradient buffer by role (0..4 = gA..gE) at the last stop; 4 activation a1 of block `index`; 5 stem output. */
 int ocl_net_debug_stop(ocl_net* net, int stage);
 int ocl_net_debug_copy(ocl_net* net, int slot, int what, int index, float* dst, int64_t max_floats,
                        int64_t* n_written, void* stream);
@@ -466,6 +466,59 @@ typedef struct {
     ocl_test_wgrad_form wform;
 } ocl_test_net_form;
 int ocl_test_net_forms(int hw, int nf, int n, int groups, int train, ocl_test_net_form* out, int cap);
+
+/* ---- the glue kernels and the head chain on their own (tests/test_gpu_aux.py) ------------------------
+ * Like the hooks above: no kernel of their own, the engine's launch_* functions, device scratch allocated and freed inside, the stream
+ * synchronised before they return.
+ *
+ * ocl_test_aux: one launcher of csrc/conv_aux.hip / csrc/bn.hip per op code.  Operands in p[], sizes in i[], scalars in f[]:
+ *   LAYOUT          p0 = const float* const xs[i0] (host list of device tensors [ns[k],3,i1,i2]), p1 = const int32_t ns[i0] (host),
+ *                   p2 = out [sum ns, i1, i2, 4]; 1 <= i0 <= 8 segments (one segment: the plain kernel, as in the engine)
+ *   AVGPOOL_FWD     p0 = z [i0,i1,i2,i3] (N,H,W,C), p1 = feat [N, C*(H/4)*(W/4)]
+ *   AVGPOOL_BWD     p0 = dfeat, p1 = dz, sizes as above
+ *   L2NORM_FWD      p0 = v [i0,i1], p1 = out, p2 = norms [i0], p3 = out2 (may be null)
+ *   L2NORM_BWD      p0 = out, p1 = norms, p2 = dout, p3 = dv; i0 rows of i1
+ *   RELU_BWD        p0 = dy, p1 = a, p2 = dx (may be dy: in place); i0 elements
+ *   COLSUM          p0 = m [i0,i1], p1 = out [i1]; i2 = accumulate
+ *   FILL            p0 = p, i0 elements of f0 (i0 == 0: returns before launching)
+ *   BN_FOLD         the whole network's BatchNorm table (i0 = hw, i1 = nf): p0 = params (ocl_net_param_count floats), p1 = running
+ *                   (ocl_net_bn_stat_count floats), p2 = out (same layout as running: scale[C], shift[C] per BatchNorm); f0 = eps
+ *   BN_APPLY_SAVED  p0 = y [i1 groups][i0 = m_per_group][i2 = C], p1 = mean [groups][C], p2 = invstd, p3 = gamma [C], p4 = beta, p5 = z */
+enum { OCL_AUX_LAYOUT = 0, OCL_AUX_AVGPOOL_FWD = 1, OCL_AUX_AVGPOOL_BWD = 2, OCL_AUX_L2NORM_FWD = 3, OCL_AUX_L2NORM_BWD = 4,
+       OCL_AUX_RELU_BWD = 5, OCL_AUX_COLSUM = 6, OCL_AUX_FILL = 7, OCL_AUX_BN_FOLD = 8, OCL_AUX_BN_APPLY_SAVED = 9 };
+typedef struct {
+    const void* p[8];
+    int64_t i[8];
+    float f[2];
+} ocl_test_aux_args;
+int ocl_test_aux(int op, const ocl_test_aux_args* a, void* stream);
+
+/* The engine's single multi-layer weight-pack launch for the whole network (hw x hw input, nf filters), with the engine's own PackDesc
+ * table.  mask: 1 forward packs, 2 data-gradient packs, 3 both.  zero_a / zero_b: two arrays of 16-byte accumulator cells the same launch
+ * clears (may be null / 0 cells: the launch has no clearing row then).  table (may be null): per layer, in module order, the 9 values
+ * w_off, tf_off, td_off, Cout, Cin, ntaps, CinP, CoutP, CiP (offsets in floats into params / arena; -1: no such pack), at most table_cap
+ * layers.  sizes (may be null): [0] floats of the parameter array, [1] floats of the arena.  arena == NULL: only fills table / sizes.
+ * The launch writes pack elements only: padding rows / columns and unselected packs keep what the caller put there.
+ * Returns the number of layers, or an error code (< 0). */
+int ocl_test_pack_all(int hw, int nf, int mask, const float* params, float* arena, void* zero_a, int64_t zero_a_cells, void* zero_b,
+                      int64_t zero_b_cells, int64_t* table, int table_cap, int64_t* sizes, void* stream);
+
+/* head_forward on a caller-supplied feature batch, then the head half of ocl_net_backward (the very function that entry point calls),
+ * for a net of the given head kind (0 linear classifier, 1 MLP, 2 linear projection, 3 none), input size and class / projection counts.
+ * params / grads: flat arrays in the net's tensor layout (ocl_net_tensor_info; n_params floats); only the head's tensors are touched.
+ * feat [n, FD], dout [n, out_dim] in; every stage tensor out: h1 [n, FD] (kind 1), h2 [n, out_dim] before normalisation (kinds 1, 2),
+ * norms [n] (kinds 1-3), out [n, out_dim], dh2 [n, out_dim] (kinds 1, 2), dh1 [n, FD] after the ReLU mask (kind 1), dfeat [n, FD]; tensors a
+ * kind does not have may be null.  The head's weight / bias gradients go to grads (accumulate as ocl_net_backward).  The stream decision
+ * is the engine's: side_stream reports whether the weight / bias gradients ran on the side stream (ocl_test_head_side_min_batch: the
+ * smallest n of an hw x hw input for which they do; 0: never in this process). */
+typedef struct {
+    int32_t head, hw, nf, n, n_classes, feat_dim, accumulate, side_stream;
+    int64_t n_params;
+    const float* params; float* grads; const float* feat; const float* dout;
+    float* h1; float* h2; float* norms; float* out; float* dh2; float* dh1; float* dfeat;
+} ocl_test_head_args;
+int ocl_test_head(ocl_test_head_args* a, void* stream);
+int ocl_test_head_side_min_batch(int hw);
 
 /* ---- which path a small-op entry point takes (tests) ------------------------------------------------
  * Host-only (no launch, no GPU): the kernel variant, grid and LDS size that the entry points of csrc/small_ops.hip choose for the

@@ -335,6 +335,16 @@ struct BnFoldDesc {
 int launch_bn_fold(const float* params, const float* running, float* out, const BnFoldDesc* descs_dev, int n_bn, float eps,
                    hipStream_t s);
 
+// The pack and fold tables of a whole Reduced-ResNet18 (hw x hw input, nf filters) exactly as the engine uploads them, with the sizes of
+// the arrays they index (net.hip; the test hooks ocl_test_pack_all and ocl_test_aux launch with them).  Host only.
+struct NetTestTables {
+    std::vector<PackDesc> pack;
+    std::vector<BnFoldDesc> fold;
+    int64_t n_params, n_stats, pack_floats;
+    int max_elems;    // the largest layer's weight count: sizes the pack launch's grid
+};
+int net_test_tables(int hw, int nf, NetTestTables* out);
+
 struct BnBwdArgs {
     const float* dz;      // grad wrt block output (post-ReLU)   [M,C]
     const float* z;       // post-ReLU output (mask); null = no ReLU mask

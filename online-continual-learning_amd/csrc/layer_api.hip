@@ -1,6 +1,7 @@
 // Kernel-level C-ABI entry points (single layers): the per-layer parity tests (tests/test_gpu_layers.py), the planner-coverage test
-// (tests/test_cpu_forms.py) and micro-benchmarks.  They plan, finalize, pack and launch through the engine's own functions; no kernel
-// lives here.
+// (tests/test_cpu_forms.py), the glue-kernel and whole-network pack-launch tests (tests/test_gpu_aux.py; ocl_test_head, which needs the
+// engine's head functions, lives in net.hip) and micro-benchmarks.  They plan, finalize, pack and launch through the engine's own
+// functions; no kernel lives here.
 #include "conv.h"
 #include <string.h>
 #include <algorithm>
@@ -339,6 +340,121 @@ int ocl_test_bn_apply_e(const float* d, const float* y, const float* mean, const
     if ((rc = launch_bn_apply_e(a, s)) != OCL_OK) return rc;
     OCL_HIP(hipStreamSynchronize(s));
     return OCL_OK;
+}
+
+int ocl_test_aux(int op, const ocl_test_aux_args* t, void* stream) {
+    OCL_REQUIRE(t, "test_aux: null arguments");
+    int rc = conv_kernels_init();
+    if (rc != OCL_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Scratch sc;
+    sc.s = s;
+    const void* const* p = t->p;
+    const int64_t* i = t->i;
+    auto F = [&](int k) { return (float*)p[k]; };
+    auto need = [&](int cnt) {
+        for (int k = 0; k < cnt; ++k)
+            if (!p[k]) return false;
+        return true;
+    };
+    switch (op) {
+        case OCL_AUX_LAYOUT: {
+            OCL_REQUIRE(need(3) && i[0] >= 1 && i[0] <= kMaxInputSegments && i[1] > 0 && i[2] > 0, "test_aux: layout arguments");
+            const float* const* xs = (const float* const*)p[0];
+            const int32_t* ns = (const int32_t*)p[1];
+            InputSegments sg;
+            memset(&sg, 0, sizeof(sg));
+            sg.n = (int)i[0];
+            int N = 0;
+            for (int k = 0; k < sg.n; ++k) {
+                OCL_REQUIRE(xs[k] && ns[k] > 0, "test_aux: layout segment %d", k);
+                sg.x[k] = xs[k];
+                sg.first[k] = N;
+                N += ns[k];
+            }
+            rc = launch_nchw3_to_nhwc4_segments(sg, F(2), N, (int)i[1], (int)i[2], s);
+            break;
+        }
+        case OCL_AUX_AVGPOOL_FWD:
+        case OCL_AUX_AVGPOOL_BWD:
+            OCL_REQUIRE(need(2) && i[0] > 0 && i[1] >= 4 && i[2] >= 4 && i[3] > 0, "test_aux: avgpool arguments");
+            rc = op == OCL_AUX_AVGPOOL_FWD ? launch_avgpool_fwd(F(0), F(1), (int)i[0], (int)i[1], (int)i[2], (int)i[3], s)
+                                           : launch_avgpool_bwd(F(0), F(1), (int)i[0], (int)i[1], (int)i[2], (int)i[3], s);
+            break;
+        case OCL_AUX_L2NORM_FWD:
+            OCL_REQUIRE(need(3) && i[0] > 0 && i[1] > 0, "test_aux: l2norm arguments");
+            rc = launch_l2norm_fwd(F(0), F(1), F(2), (int)i[0], (int)i[1], s, F(3));
+            break;
+        case OCL_AUX_L2NORM_BWD:
+            OCL_REQUIRE(need(4) && i[0] > 0 && i[1] > 0, "test_aux: l2norm arguments");
+            rc = launch_l2norm_bwd(F(0), F(1), F(2), F(3), (int)i[0], (int)i[1], s);
+            break;
+        case OCL_AUX_RELU_BWD:
+            OCL_REQUIRE(need(3) && i[0] > 0, "test_aux: relu_bwd arguments");
+            rc = launch_relu_bwd(F(0), F(1), F(2), i[0], s);
+            break;
+        case OCL_AUX_COLSUM:
+            OCL_REQUIRE(need(2) && i[0] > 0 && i[1] > 0, "test_aux: colsum arguments");
+            rc = launch_colsum(F(0), (int)i[0], (int)i[1], F(1), (int)i[2], s);
+            break;
+        case OCL_AUX_FILL:
+            OCL_REQUIRE(need(1) && i[0] >= 0, "test_aux: fill arguments");
+            rc = launch_fill(F(0), i[0], t->f[0], s);
+            break;
+        case OCL_AUX_BN_FOLD: {
+            OCL_REQUIRE(need(3), "test_aux: bn_fold arguments");
+            NetTestTables nt;
+            if ((rc = net_test_tables((int)i[0], (int)i[1], &nt)) != OCL_OK) return rc;
+            const size_t bytes = nt.fold.size() * sizeof(BnFoldDesc);
+            BnFoldDesc* dev = (BnFoldDesc*)sc.take(bytes, 0);
+            if (!dev) { set_error("test_aux: out of device memory"); return OCL_ERR_HIP; }
+            OCL_HIP(hipMemcpyAsync(dev, nt.fold.data(), bytes, hipMemcpyHostToDevice, s));
+            rc = launch_bn_fold(F(0), F(1), F(2), dev, (int)nt.fold.size(), t->f[0], s);
+            OCL_HIP(hipStreamSynchronize(s));   // (the host table goes out of scope)
+            break;
+        }
+        case OCL_AUX_BN_APPLY_SAVED:
+            OCL_REQUIRE(need(6) && i[0] > 0 && i[1] > 0 && i[2] > 0 && i[2] % 4 == 0, "test_aux: bn_apply_saved arguments");
+            rc = launch_bn_apply_saved(F(0), F(1), F(2), F(3), F(4), F(5), i[0], (int)i[1], (int)i[2], s);
+            break;
+        default:
+            set_error("test_aux: op=%d", op);
+            return OCL_ERR_ARG;
+    }
+    if (rc != OCL_OK) return rc;
+    OCL_HIP(hipStreamSynchronize(s));
+    return OCL_OK;
+}
+
+int ocl_test_pack_all(int hw, int nf, int mask, const float* params, float* arena, void* zero_a, int64_t zero_a_cells, void* zero_b,
+                      int64_t zero_b_cells, int64_t* table, int table_cap, int64_t* sizes, void* stream) {
+    OCL_REQUIRE(mask >= 1 && mask <= PACK_ALL && zero_a_cells >= 0 && zero_b_cells >= 0, "test_pack_all: mask=%d", mask);
+    OCL_REQUIRE((zero_a || !zero_a_cells) && (zero_b || !zero_b_cells), "test_pack_all: cells without an array");
+    NetTestTables nt;
+    int rc = net_test_tables(hw, nf, &nt);
+    if (rc != OCL_OK) return rc;
+    const int L = (int)nt.pack.size();
+    for (int l = 0; table && l < L && l < table_cap; ++l) {
+        const PackDesc& d = nt.pack[l];
+        const int64_t row[9] = {d.w_off, d.tf_off, d.td_off, d.Cout, d.Cin, d.ntaps, d.CinP, d.CoutP, d.CiP};
+        memcpy(table + (size_t)l * 9, row, sizeof(row));
+    }
+    if (sizes) {
+        sizes[0] = nt.n_params;
+        sizes[1] = nt.pack_floats;
+    }
+    if (!arena) return L;
+    OCL_REQUIRE(params, "test_pack_all: null params");
+    if ((rc = conv_kernels_init()) != OCL_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Scratch sc;
+    sc.s = s;
+    PackDesc* dev = (PackDesc*)sc.take((size_t)L * sizeof(PackDesc), 0);
+    if (!dev) { set_error("test_pack_all: out of device memory"); return OCL_ERR_HIP; }
+    OCL_HIP(hipMemcpyAsync(dev, nt.pack.data(), (size_t)L * sizeof(PackDesc), hipMemcpyHostToDevice, s));
+    rc = launch_pack_weights(params, arena, dev, L, nt.max_elems, s, mask, (StatCell*)zero_a, zero_a_cells, (StatCell*)zero_b, zero_b_cells);
+    OCL_HIP(hipStreamSynchronize(s));
+    return rc == OCL_OK ? L : rc;
 }
 
 int ocl_set_deterministic(int on) { return set_deterministic_sums(on); }

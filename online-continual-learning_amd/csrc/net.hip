@@ -481,8 +481,12 @@ static int get_plans(ocl_net* n, int N, int groups, PlanSet** out) {
 }
 
 // -----------------------------------------------------------------------------------------------------
-static int upload_descs(ocl_net* n, hipStream_t s) {
-    std::vector<PackDesc> pd(n->convs.size());
+// the two device tables of a network: one PackDesc per convolution, one BnFoldDesc per BatchNorm (also what ocl_test_pack_all / ocl_test_aux's
+// bn_fold launch with, through net_test_tables)
+static void make_descs(const ocl_net* n, std::vector<PackDesc>* pdv, std::vector<BnFoldDesc>* fdv) {
+    std::vector<PackDesc>& pd = *pdv;
+    std::vector<BnFoldDesc>& fd = *fdv;
+    pd.assign(n->convs.size(), PackDesc());
     for (size_t i = 0; i < n->convs.size(); ++i) {
         const ConvInfo& c = n->convs[i];
         pd[i].w_off = n->tensors[c.w_t].off;
@@ -495,7 +499,7 @@ static int upload_descs(ocl_net* n, hipStream_t s) {
         pd[i].CoutP = c.CoutP;
         pd[i].CiP = c.CiP;
     }
-    std::vector<BnFoldDesc> fd(n->bns.size());
+    fd.assign(n->bns.size(), BnFoldDesc());
     for (size_t i = 0; i < n->bns.size(); ++i) {
         fd[i].gamma_off = n->tensors[n->bns[i].gamma_t].off;
         fd[i].beta_off = n->tensors[n->bns[i].beta_t].off;
@@ -503,6 +507,17 @@ static int upload_descs(ocl_net* n, hipStream_t s) {
         fd[i].out_off = n->bns[i].stat_off;
         fd[i].C = n->bns[i].C;
     }
+}
+// (the grid of the pack launch is sized for the largest layer)
+static int pack_max_elems(const ocl_net* n) {
+    int max_elems = 0;
+    for (auto& c : n->convs) max_elems = std::max(max_elems, c.Cout * c.Cin * c.k * c.k);
+    return max_elems;
+}
+static int upload_descs(ocl_net* n, hipStream_t s) {
+    std::vector<PackDesc> pd;
+    std::vector<BnFoldDesc> fd;
+    make_descs(n, &pd, &fd);
     unsigned char* dst = n->ws + n->off_descs;
     OCL_HIP(hipMemcpyAsync(dst, pd.data(), pd.size() * sizeof(PackDesc), hipMemcpyHostToDevice, s));
     OCL_HIP(hipMemcpyAsync(dst + align_up((int64_t)(pd.size() * sizeof(PackDesc)), 64), fd.data(), fd.size() * sizeof(BnFoldDesc),
@@ -646,6 +661,61 @@ static int side_join(ocl_net* n, hipStream_t s) {
     OCL_HIP(hipEventRecord(e, n->s2));
     OCL_HIP(hipStreamWaitEvent(s, e, 0));
     return OCL_OK;
+}
+
+// kTwoStreamMinBatch x 32 x 32 input pixels: the smallest pass whose weight gradients leave the caller's stream.  Debug stops and
+// measurement runs (ocl_prof_enable, OCL_SINGLE_STREAM=1: per-kernel durations of the kernel alone) stay on one stream.
+static bool two_streams_at(int64_t in_pixels, int dbg_stop) {
+    static const bool env_single = [] { const char* e = getenv("OCL_SINGLE_STREAM"); return e && e[0] == '1'; }();
+    return dbg_stop < 0 && in_pixels >= (int64_t)kTwoStreamMinBatch * 1024 && !prof_on() && !env_single;
+}
+// ... and the smallest whose head dW / db (and projection shortcuts) go to the side stream
+static bool head_side_at(int64_t in_pixels, bool two_streams) { return two_streams && in_pixels >= (int64_t)kSideExtraMinBatch * 1024; }
+static bool backward_two_streams(const ocl_net* n, int N) { return two_streams_at((int64_t)N * n->d.in_h * n->d.in_w, n->dbg_stop); }
+static bool head_on_side_stream(const ocl_net* n, int N, bool two_streams) {
+    return head_side_at((int64_t)N * n->d.in_h * n->d.in_w, two_streams);
+}
+
+// The tensors of the head's backward: the tape of head_forward, the incoming gradient, and where the stage gradients go.
+struct HeadBwd {
+    const float *feat, *h1, *out, *norms, *dout;
+    float *dfeat, *dh1, *dh2;
+};
+// Head half of the backward (ocl_net_backward; ocl_test_head runs it on caller-supplied tensors): dL/dfeat from dL/dout, and the head's
+// weight and bias gradients into the flat gradient array Gr (accumulate = 0: overwritten, encoder.linear of a SupConResNet zeroed).
+// two_streams: the pass has a side stream (ensure_side_stream has run); the head's dW / db go there from kSideExtraMinBatch on.
+static int head_backward(ocl_net* n, const float* P, float* Gr, const HeadBwd& t, int N, int accumulate, hipStream_t s, bool two_streams) {
+    auto T = [&](int i) { return P + n->tensors[i].off; };
+    auto GT = [&](int i) { return Gr + n->tensors[i].off; };
+    const int FD = n->feat_dim, OD = n->out_dim;
+    auto lin_bwd = [&](const float* dy, int ncol, const float* xin, int kin, int tw, int tb, float* dx) -> int {
+        // y = x W^T + b, W [ncol, kin]
+        const bool hs = head_on_side_stream(n, N, two_streams);
+        hipStream_t sw = hs ? n->s2 : s;
+        int r = hs ? side_wait(n, s) : OCL_OK;   // dy is complete
+        if (r) return r;
+        if ((r = ocl_gemm_small(dy, 1, ncol, xin, kin, 1, GT(tw), kin, ncol, kin, N, nullptr, 0, accumulate, sw))) return r;  // dW = dy^T x
+        if ((r = launch_colsum(dy, N, ncol, GT(tb), accumulate, sw))) return r;
+        if (dx) r = ocl_gemm_small(dy, ncol, 1, T(tw), kin, 1, dx, kin, N, kin, ncol, nullptr, 0, 0, s);  // dx = dy W
+        return r;
+    };
+    int rc = OCL_OK;
+    if (n->d.head == 0) return lin_bwd(t.dout, OD, t.feat, FD, n->t_linear_w, n->t_linear_b, t.dfeat);
+    if (!accumulate) {  // encoder.linear takes no part in SupConResNet.forward: its gradient is zero
+        // (weight and bias are neighbours in the flat array: one fill)
+        if ((rc = launch_fill(GT(n->t_linear_w), n->tensors[n->t_linear_w].numel + n->tensors[n->t_linear_b].numel, 0.f, s))) return rc;
+    }
+    if (n->d.head == 1) {
+        if ((rc = launch_l2norm_bwd(t.out, t.norms, t.dout, t.dh2, N, OD, s))) return rc;
+        if ((rc = lin_bwd(t.dh2, OD, t.h1, FD, n->t_h2_w, n->t_h2_b, t.dh1))) return rc;
+        if ((rc = launch_relu_bwd(t.dh1, t.h1, t.dh1, (int64_t)N * FD, s))) return rc;
+        return lin_bwd(t.dh1, FD, t.feat, FD, n->t_h0_w, n->t_h0_b, t.dfeat);
+    }
+    if (n->d.head == 2) {
+        if ((rc = launch_l2norm_bwd(t.out, t.norms, t.dout, t.dh2, N, OD, s))) return rc;
+        return lin_bwd(t.dh2, OD, t.feat, FD, n->t_h2_w, n->t_h2_b, t.dfeat);
+    }
+    return launch_l2norm_bwd(t.out, t.norms, t.dout, t.dfeat, N, FD, s);
 }
 
 // -----------------------------------------------------------------------------------------------------
@@ -970,8 +1040,7 @@ int ocl_net_forward_segments(ocl_net* n, const float* const* xs, const int32_t* 
     int rc = get_plans(n, Nplan, train ? groups : 1, &ps);
     if (rc != OCL_OK) return rc;
     float* pack = (float*)(n->ws + n->off_pack);
-    int max_elems = 0;
-    for (auto& c : n->convs) max_elems = std::max(max_elems, c.Cout * c.Cin * c.k * c.k);
+    const int max_elems = pack_max_elems(n);
     // every forward packs (the caller may have stepped the weights), but only the layouts the pass reads: the forward packs, and the
     // data-gradient packs when a backward will follow this tape
     // (OCL_FWD_PACK_ALL: the caller will run more passes on these weights, a taped one among them: pack for the backward now as well)
@@ -1481,8 +1550,6 @@ int ocl_net_backward(ocl_net* n, int slot, const float* dout, int accumulate, vo
     const int repack_mask = n->pack_need_fwd | n->pack_need_bwd;
     const bool bsums_dirty = !n->bsums_clean;   // a second backward since the last forward: trunk_backward clears the arena itself
     const bool replay = graph_enabled(n);
-    auto T = [&](int t) { return P + n->tensors[t].off; };
-    auto GT = [&](int t) { return Gr + n->tensors[t].off; };
     const int FD = n->feat_dim, OD = n->out_dim;
     float* hb = (float*)(n->ws + n->off_head);
     float* dfeat = hb;
@@ -1505,49 +1572,18 @@ int ocl_net_backward(ocl_net* n, int slot, const float* dout, int accumulate, vo
     // trunk come from a ring, a slot is rewritten only after the event behind its last weight-gradient reader.  Replay batches of
     // 10-20 images are latency-bound: the event traffic costs more than the overlap returns there.  Debug stops and measurement
     // runs (ocl_prof_enable, OCL_SINGLE_STREAM=1: per-kernel durations of the kernel alone) stay on one stream as well.
-    static const bool env_single = [] { const char* e = getenv("OCL_SINGLE_STREAM"); return e && e[0] == '1'; }();
-    // kTwoStreamMinBatch x 32 x 32 input pixels: the smallest pass whose weight gradients leave the caller's stream
-    const bool two_streams = n->dbg_stop < 0 && (int64_t)N * n->d.in_h * n->d.in_w >= (int64_t)kTwoStreamMinBatch * 1024 && !prof_on() && !env_single;
+    const bool two_streams = backward_two_streams(n, N);
     if (two_streams && (rc = ensure_side_stream(n))) return rc;
-    auto lin_bwd = [&](const float* dy, int ncol, const float* xin, int kin, int tw, int tb, float* dx) -> int {
-        // y = x W^T + b, W [ncol, kin]
-        const bool hs_big = (int64_t)N * n->d.in_h * n->d.in_w >= (int64_t)kSideExtraMinBatch * 1024;
-        const bool hs = two_streams && hs_big;
-        hipStream_t sw = hs ? n->s2 : s;
-        int r = hs ? side_wait(n, s) : OCL_OK;   // dy is complete
-        if (r) return r;
-        if ((r = ocl_gemm_small(dy, 1, ncol, xin, kin, 1, GT(tw), kin, ncol, kin, N, nullptr, 0, accumulate, sw))) return r;  // dW = dy^T x
-        if ((r = launch_colsum(dy, N, ncol, GT(tb), accumulate, sw))) return r;
-        if (dx) r = ocl_gemm_small(dy, ncol, 1, T(tw), kin, 1, dx, kin, N, kin, ncol, nullptr, 0, 0, s);  // dx = dy W
-        return r;
-    };
+    HeadBwd hd;
+    hd.feat = feat; hd.h1 = h1; hd.out = o; hd.norms = norms; hd.dout = dout;
+    hd.dfeat = dfeat; hd.dh1 = dh1; hd.dh2 = dh2;
     const bool fused_tape = n->slot_fused[slot];
     auto body = [&]() -> int {
         int rc = OCL_OK;
         if (repack) {
-            int max_elems = 0;
-            for (auto& c : n->convs) max_elems = std::max(max_elems, c.Cout * c.Cin * c.k * c.k);
-            if ((rc = launch_pack_weights(P, pack, pack_descs(n), (int)n->convs.size(), max_elems, s, repack_mask))) return rc;
+            if ((rc = launch_pack_weights(P, pack, pack_descs(n), (int)n->convs.size(), pack_max_elems(n), s, repack_mask))) return rc;
         }
-        if (n->d.head == 0) {
-            if ((rc = lin_bwd(dout, OD, feat, FD, n->t_linear_w, n->t_linear_b, dfeat))) return rc;
-        } else {
-            if (!accumulate) {  // encoder.linear takes no part in SupConResNet.forward: its gradient is zero
-                // (weight and bias are neighbours in the flat array: one fill)
-                if ((rc = launch_fill(GT(n->t_linear_w), n->tensors[n->t_linear_w].numel + n->tensors[n->t_linear_b].numel, 0.f, s))) return rc;
-            }
-            if (n->d.head == 1) {
-                if ((rc = launch_l2norm_bwd(o, norms, dout, dh2, N, OD, s))) return rc;
-                if ((rc = lin_bwd(dh2, OD, h1, FD, n->t_h2_w, n->t_h2_b, dh1))) return rc;
-                if ((rc = launch_relu_bwd(dh1, h1, dh1, (int64_t)N * FD, s))) return rc;
-                if ((rc = lin_bwd(dh1, FD, feat, FD, n->t_h0_w, n->t_h0_b, dfeat))) return rc;
-            } else if (n->d.head == 2) {
-                if ((rc = launch_l2norm_bwd(o, norms, dout, dh2, N, OD, s))) return rc;
-                if ((rc = lin_bwd(dh2, OD, feat, FD, n->t_h2_w, n->t_h2_b, dfeat))) return rc;
-            } else {
-                if ((rc = launch_l2norm_bwd(o, norms, dout, dfeat, N, FD, s))) return rc;
-            }
-        }
+        if ((rc = head_backward(n, P, Gr, hd, N, accumulate, s, two_streams))) return rc;
         // ---- trunk ------------------------------------------------------------------------------------
         n->bsums_clean = !bsums_dirty;   // (trunk_backward reads the flag: the same decision whenever the sequence is issued)
         return trunk_backward(n, ps, P, Gr, S, N, G, accumulate, dfeat, s, two_streams ? n->s2 : nullptr, frozen, fused_tape);
@@ -1620,6 +1656,53 @@ int ocl_test_net_forms(int hw, int nf, int N, int groups, int train, ocl_test_ne
     return rc == OCL_OK ? cnt : rc;
 }
 
+int ocl_test_head_side_min_batch(int hw) {
+    OCL_REQUIRE(hw >= 32, "test_head_side_min_batch: hw=%d", hw);
+    const int64_t px = (int64_t)hw * hw;
+    const int64_t need = (int64_t)std::max(kTwoStreamMinBatch, kSideExtraMinBatch) * 1024;
+    const int N = (int)std::max<int64_t>(1, (need + px - 1) / px);
+    return head_side_at(N * px, two_streams_at(N * px, -1)) ? N : 0;   // (0: measurement modes keep every pass on one stream)
+}
+
+int ocl_test_head(ocl_test_head_args* a, void* stream) {
+    OCL_REQUIRE(a && a->params && a->grads && a->feat && a->dout && a->out && a->dfeat, "test_head: null pointer");
+    OCL_REQUIRE(a->head >= 0 && a->head <= 3 && a->n > 0 && a->hw >= 32 && a->nf > 0, "test_head: head=%d n=%d hw=%d nf=%d", a->head, a->n, a->hw, a->nf);
+    OCL_REQUIRE(a->head == 0 || a->norms, "test_head: norms");
+    OCL_REQUIRE((a->head != 1 && a->head != 2) || (a->h2 && a->dh2), "test_head: h2 / dh2");
+    OCL_REQUIRE(a->head != 1 || (a->h1 && a->dh1), "test_head: h1 / dh1");
+    ocl_net_desc d;
+    memset(&d, 0, sizeof(d));
+    d.in_h = d.in_w = a->hw; d.nf = a->nf; d.n_classes = a->n_classes; d.head = a->head; d.feat_dim = a->feat_dim; d.max_batch = a->n; d.n_slots = 1;
+    ocl_net* n = nullptr;
+    int rc = ocl_net_create(&d, &n);
+    if (rc != OCL_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int N = a->n;
+    if (a->n_params != n->n_params) {
+        set_error("test_head: the flat arrays hold %lld floats, the net's %lld", (long long)a->n_params, (long long)n->n_params);
+        rc = OCL_ERR_ARG;
+    }
+    bool wrote = false;
+    if (rc == OCL_OK)
+        rc = head_forward(n, a->params, (float*)a->feat, a->h1, a->h2, a->norms, a->out, N, s, nullptr, &wrote);
+    const bool two_streams = backward_two_streams(n, N);
+    if (rc == OCL_OK && two_streams) rc = ensure_side_stream(n);
+    if (rc == OCL_OK) {
+        HeadBwd hd;
+        hd.feat = a->feat; hd.h1 = a->h1; hd.out = a->out; hd.norms = a->norms; hd.dout = a->dout;
+        hd.dfeat = a->dfeat; hd.dh1 = a->dh1; hd.dh2 = a->dh2;
+        rc = head_backward(n, a->params, a->grads, hd, N, a->accumulate, s, two_streams);
+        a->side_stream = head_on_side_stream(n, N, two_streams) ? 1 : 0;
+    }
+    if (n->s2) (void)hipStreamSynchronize(n->s2);
+    if (hipStreamSynchronize(s) != hipSuccess && rc == OCL_OK) {
+        set_error("test_head: %s", hipGetErrorString(hipGetLastError()));
+        rc = OCL_ERR_HIP;
+    }
+    ocl_net_destroy(n);
+    return rc;
+}
+
 int ocl_net_debug_stop(ocl_net* n, int stage) {
     OCL_REQUIRE(n, "debug_stop: null net");
     n->dbg_stop = stage;
@@ -1678,3 +1761,23 @@ int ocl_net_debug_copy(ocl_net* n, int slot, int what, int index, float* dst, in
 }
 
 }  // extern "C"
+
+namespace ocl {
+
+int net_test_tables(int hw, int nf, NetTestTables* out) {
+    ocl_net_desc d;
+    memset(&d, 0, sizeof(d));
+    d.in_h = d.in_w = hw; d.nf = nf; d.n_classes = 10; d.head = 0; d.max_batch = 1; d.n_slots = 1;
+    ocl_net* n = nullptr;
+    int rc = ocl_net_create(&d, &n);
+    if (rc != OCL_OK) return rc;
+    make_descs(n, &out->pack, &out->fold);
+    out->n_params = n->n_params;
+    out->n_stats = n->n_stats;
+    out->pack_floats = n->pack_floats;
+    out->max_elems = pack_max_elems(n);
+    ocl_net_destroy(n);
+    return OCL_OK;
+}
+
+}  // namespace ocl

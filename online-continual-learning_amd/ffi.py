@@ -77,6 +77,16 @@ class TestNetForm(C.Structure):
                                                                    ("wdesc", TestWgradDesc), ("wform", TestWgradForm)]
 
 
+class TestAuxArgs(C.Structure):
+    """ocl_test_aux_args: operands p[], sizes i[], scalars f[] of one launcher (tests/test_gpu_aux.py)."""
+    _fields_ = [("p", vp * 8), ("i", i64 * 8), ("f", f32 * 2)]
+
+
+class TestHeadArgs(C.Structure):
+    _fields_ = _ints("head", "hw", "nf", "n", "n_classes", "feat_dim", "accumulate", "side_stream") + [("n_params", i64)] + \
+               [(n, vp) for n in ("params", "grads", "feat", "dout", "h1", "h2", "norms", "out", "dh2", "dh1", "dfeat")]
+
+
 class SmallOpPlan(C.Structure):
     """ocl_small_op_plan: what ocl_test_small_op_path reports (tests/test_cpu_small_ops.py, tests/test_gpu_small_ops.py)."""
     _fields_ = [("path", i32), ("aux", i32), ("grid_x", C.c_uint32), ("grid_y", C.c_uint32), ("block", C.c_uint32),
@@ -148,6 +158,10 @@ SIGNATURES = {
     "ocl_test_bn_bwd": (C.c_int, [C.POINTER(TestBnBwdArgs), vp]),
     "ocl_test_bn_apply_e": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     "ocl_test_net_forms": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TestNetForm), C.c_int]),
+    "ocl_test_aux": (C.c_int, [C.c_int, C.POINTER(TestAuxArgs), vp]),
+    "ocl_test_pack_all": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, i64, vp, i64, C.POINTER(i64), C.c_int, C.POINTER(i64), vp]),
+    "ocl_test_head": (C.c_int, [C.POINTER(TestHeadArgs), vp]),
+    "ocl_test_head_side_min_batch": (C.c_int, [C.c_int]),
     "ocl_test_small_op_path": (C.c_int, [C.c_int, C.POINTER(i64), C.c_int, C.POINTER(SmallOpPlan)]),
     "ocl_prof_enable": (C.c_int, [C.c_int]),
     "ocl_prof_reset": (C.c_int, []),

@@ -62,6 +62,9 @@ CASES = [
     ("ER", "mini_imagenet", None, 6, 1),
     ("ER", "mini_imagenet", None, 20, 2),
     ("SCR", "cifar100", "linear", 8, 2),
+    ("SCR", "cifar100", "None", 8, 2),          # SupConResNet(head='None'): normalised features, out_dim = feature_dim
+    ("SCR", "mini_imagenet", "mlp", 4, 2),      # the 640-wide MLP head; the 11 x 11 final map cropped to 8 x 8 by avg_pool2d(4)
+    ("SCR", "cifar100", "linear", 36, 2),
 ]
 
 BLOCKS = ["layer%d.%d" % (l, b) for l in range(1, 5) for b in range(2)]
@@ -212,7 +215,8 @@ def test_gradient_accumulation_and_zero_grad_semantics(cuda):
         off += p.numel()
 
 
-@pytest.mark.parametrize("agent,data,head,n", [("ER", "cifar100", None, 70), ("SCR", "cifar100", "mlp", 33), ("ER", "mini_imagenet", None, 5)])
+@pytest.mark.parametrize("agent,data,head,n", [("ER", "cifar100", None, 70), ("SCR", "cifar100", "mlp", 33), ("ER", "mini_imagenet", None, 5),
+                                               ("SCR", "mini_imagenet", "mlp", 5)])
 def test_eval_forward_features_vs_oracle(cuda, agent, data, head, n):
     """eval-mode (running statistics) features / outputs: the ASER scoring and NCM path (utils/utils.py:45-90)."""
     hw = 84 if data == "mini_imagenet" else 32

@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 import augment_ref as AR
+import parity_bounds as PB
 import small_op_cases as SC
 from guarded import Guarded
 
@@ -103,38 +104,13 @@ def find(op, name):
     return [c for c in SC.CASES[op] if c["name"] == name][0]
 
 
-def ulp32(x):
-    return float(np.spacing(np.float32(abs(x)))) if x else 2.0 ** -149
-
-
-def record(case, tensor, err, e_ref, bound):
-    REPORT.append((case, tensor, err, "-" if e_ref is None else "%.4g" % e_ref, bound, err / bound if bound else (0.0 if err == 0 else float("inf"))))
-
-
 def check_vs_torch32(case, tensor, got, ref64, ref32, cap=None):
-    """Transcendental kernels: error <= max(4 * e_ref, 4 ulp of the largest |reference| element)."""
-    got, ref64, ref32 = (np.asarray(a, dtype=np.float64) for a in (got, ref64, ref32))
-    assert got.shape == ref64.shape == ref32.shape, (got.shape, ref64.shape, ref32.shape)
-    assert np.isfinite(got).all(), "%s %s: non-finite output" % (case, tensor)
-    err = float(np.abs(got - ref64).max())
-    e_ref = float(np.abs(ref32 - ref64).max())
-    bound = max(4 * e_ref, 4 * ulp32(np.abs(ref64).max()))
-    if cap is not None:
-        bound = min(bound, cap)
-    record(case, tensor, err, e_ref, bound)
-    print("%s %s: kernel error %.4g, torch fp32 error %.4g, bound %.4g" % (case, tensor, err, e_ref, bound))
-    assert err <= bound, "%s %s: error %.4g against float64 exceeds %.4g (torch fp32: %.4g)" % (case, tensor, err, bound, e_ref)
+    """Transcendental kernels: error <= max(4 * e_ref, 4 ulp of the largest |reference| element) (tests/parity_bounds.py)."""
+    PB.check_vs_torch32(REPORT, case, tensor, got, ref64, ref32, cap)
 
 
 def check_derived(case, tensor, got, ref64, bound):
-    got, ref64, bound = (np.asarray(a, dtype=np.float64) for a in (got, ref64, bound))
-    assert np.isfinite(got).all(), "%s %s: non-finite output" % (case, tensor)
-    err = np.abs(got - ref64)
-    i = int(np.argmax(err - bound))
-    e, b = float(err.reshape(-1)[i]), float(np.broadcast_to(bound, err.shape).reshape(-1)[i])
-    record(case, tensor, e, None, b)
-    print("%s %s: worst element error %.4g, bound %.4g" % (case, tensor, e, b))
-    assert (err <= bound).all(), "%s %s: error %.4g exceeds the derived bound %.4g" % (case, tensor, e, b)
+    PB.check_derived(REPORT, case, tensor, got, ref64, bound)
 
 
 # ==========================================================================================================================================

@@ -167,6 +167,24 @@ int ocl_ce_segmented_fwd_bwd(const float* logits, const int64_t* y, const int32_
 int ocl_kd_fwd_bwd(const float* scores, const float* target_scores, int n, int c, float T, float* loss_out, float* dscores,
                    void* stream);
 
+/* ---- K6b: cross-entropy blended with distillation (Learning without Forgetting) ------------------------
+ * agents/lwf.py:36-39 with utils/kd_manager.py:6-11 and agents/base.py:113, loss and gradient in ONE launch:
+ *   ce = mean_r(lse(s_r) - s_r[y_r])
+ *   kd = mean_r(-sum_j softmax(t_r/T)_j * log_softmax(s_r/T)_j) * T^2          (s = logits, t = teacher)
+ *   loss_out[3] = {w_new * ce + w_old * kd, ce, kd}
+ *   dlogits[r][j] = w_new * (softmax(s_r)_j - [j == y_r]) / n + w_old * (softmax(s_r/T)_j - softmax(t_r/T)_j) * T / n
+ * x / T is a true division, as in ocl_kd_fwd_bwd.  teacher == NULL (LwF's first task, where the reference
+ * computes 1 * loss_new + 0 * 0): kd = 0 and the gradient is the CE term alone; with w_new == 1 the
+ * cross-entropy and dlogits are then the bits of ocl_ce_fwd_bwd(reduction = mean).  A teacher that equals the
+ * logits bit for bit adds exactly 0 to the gradient.  dlogits may be NULL (losses only: the same three values).
+ * One workgroup, one wave per row, sums in a fixed order without atomics: two runs give the same bits.  A row
+ * of up to 256 columns is read once and held in registers; a longer one is re-read by strided loops.  Ordered
+ * on `stream`, no host synchronisation.  OCL_ERR_ARG ("ce_kd_blend: ...") before any launch, nothing written,
+ * for n < 1, c < 1, T <= 0, a non-finite T, w_new or w_old, a null logits, y or loss_out, or a dlogits that
+ * overlaps logits or teacher. */
+int ocl_ce_kd_blend_fwd_bwd(const float* logits, const int64_t* y, const float* teacher, int n, int c, float T, float w_new,
+                            float w_old, float* loss_out, float* dlogits, void* stream);
+
 /* ---- K7: supervised contrastive loss ---------------------------------------------------------------
  * SupConLoss.forward with contrast_mode='all' (utils/loss.py:19-96).  feat is VIEW-MAJOR
  * [n_views*bsz, dim] (= torch.cat(torch.unbind(features,1)), loss.py:56).  workspace: at least

@@ -17,10 +17,17 @@ class KdManager:
         self._owner = model
         self.teacher_model = model.flat_params().detach().clone()
 
+    def teacher_logits(self, x):
+        """The teacher's logits for x (no autograd node; the student's running statistics stay as they are), or None before the first
+        snapshot."""
+        if self.teacher_model is None:
+            return None
+        with torch.no_grad():
+            return self._owner.forward_with_params(x, self.teacher_model)
+
     def get_kd_loss(self, cur_model_logits, x):
         if self.teacher_model is not None:
-            with torch.no_grad():
-                prev_model_logits = self._owner.forward_with_params(x, self.teacher_model)
+            prev_model_logits = self.teacher_logits(x)
             dist_loss = loss_fn_kd(cur_model_logits, prev_model_logits)
         else:
             dist_loss = 0

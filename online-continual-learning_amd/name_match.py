@@ -43,6 +43,13 @@ regularization_agents = _Lazy({
 })
 
 
+# regularisation by distillation against last task's model: no replay memory either; the teacher is KdManager's parameter snapshot
+# (section 1b as well; a table of its own because tests/test_cpu_ewc.py pins `regularization_agents` to EWC alone)
+distillation_agents = _Lazy({
+    'LWF': ('.agents.lwf', 'Lwf'),
+})
+
+
 # agents that train offline on their memory at every task's end (section 1b as well)
 offline_agents = _Lazy({
     'GDUMB': ('.agents.gdumb', 'Gdumb'),
@@ -50,9 +57,9 @@ offline_agents = _Lazy({
 
 
 def get_agent(key):
-    """The agent class registered under `key`: `agents` first, then `extra_agents`, `regularization_agents` and `offline_agents`;
-    KeyError otherwise."""
-    for table in (agents, extra_agents, regularization_agents, offline_agents):
+    """The agent class registered under `key`: `agents` first, then `extra_agents`, `regularization_agents`, `distillation_agents` and
+    `offline_agents`; KeyError otherwise."""
+    for table in (agents, extra_agents, regularization_agents, distillation_agents, offline_agents):
         if key in table:
             return table[key]
     raise KeyError(key)

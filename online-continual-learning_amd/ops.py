@@ -330,6 +330,39 @@ def kd_loss(scores, target_scores, T=2.0, want_grad=True):
     return loss[0], ds
 
 
+# ---- K6b ---------------------------------------------------------------------------------------------
+def ce_kd_blend(logits, y, teacher_logits, T, w_new, w_old, want_grad=True, dl_out=None):
+    """(loss3, dlogits) of Learning without Forgetting's loss (agents/lwf.py:36-39) in one launch: loss3 = [w_new * ce + w_old * kd, ce, kd]
+    with ce the mean cross-entropy of `logits` against `y` and kd loss_fn_kd(logits, teacher_logits, T); dlogits the gradient of
+    loss3[0].  teacher_logits None (no teacher yet): kd = 0, the gradient is the cross-entropy's.  Nothing is made contiguous or
+    converted here: a tensor of another dtype, shape, layout or device is refused.  dl_out: a contiguous float32 [n, c] tensor (e.g. a
+    row block of a larger gradient buffer) that receives dlogits instead of a fresh one."""
+    def refuse(what, t, dtype, shape):
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise RuntimeError("ce_kd_blend: %s must be a contiguous %s tensor of shape %s, got %s %s%s" % (
+                what, dtype, tuple(shape), getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ())),
+                "" if not torch.is_tensor(t) or t.is_contiguous() else " (not contiguous)"))
+
+    if not torch.is_tensor(logits) or logits.dim() != 2:
+        raise RuntimeError("ce_kd_blend: logits must be a [n, c] tensor")
+    refuse("logits", logits, torch.float32, logits.shape)
+    n, c = logits.shape
+    refuse("y", y, torch.int64, (n,))
+    if teacher_logits is not None:
+        refuse("teacher_logits", teacher_logits, torch.float32, (n, c))
+    if dl_out is not None:
+        refuse("dl_out", dl_out, torch.float32, (n, c))
+    for what, t in (("logits", logits), ("y", y), ("teacher_logits", teacher_logits), ("dl_out", dl_out)):
+        if t is not None and (not t.is_cuda or t.device != logits.device):
+            raise RuntimeError("ce_kd_blend: %s is on %s; every tensor lives on the logits' GPU" % (what, t.device))
+    ffi.init()
+    loss = torch.empty(3, dtype=torch.float32, device=logits.device)
+    dl = dl_out if dl_out is not None else (torch.empty_like(logits) if want_grad else None)
+    ffi.check(ffi.lib().ocl_ce_kd_blend_fwd_bwd(ffi.ptr(logits), ffi.ptr(y), ffi.ptr(teacher_logits), n, c, float(T), float(w_new), float(w_old),
+                                                ffi.ptr(loss), ffi.ptr(dl), ffi.stream()), "ce_kd_blend")
+    return loss, dl
+
+
 # ---- K7 ----------------------------------------------------------------------------------------------
 def supcon(feat_view_major, y, n_views, temperature, want_grad=True):
     """(loss, dfeat) for view-major features [n_views*bsz, dim] (utils/loss.py:19-96)."""

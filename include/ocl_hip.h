@@ -185,6 +185,30 @@ int ocl_kd_fwd_bwd(const float* scores, const float* target_scores, int n, int c
 int ocl_ce_kd_blend_fwd_bwd(const float* logits, const int64_t* y, const float* teacher, int n, int c, float T, float w_new,
                             float w_old, float* loss_out, float* dlogits, void* stream);
 
+/* ---- K6c: binary cross-entropy against a distilled target (iCaRL) ----------------------------------------
+ * agents/icarl.py:42-62, loss and gradient in ONE launch.  s = logits [n, c], t = teacher [n, c],
+ * sig(x) = 1 / (1 + exp(-x)); the first n_stream rows are the stream batch, the others memory rows:
+ *   z[r][j] = sig(t[r][j])                                   for j <  n_old          (every row)
+ *           = 1 if r < n_stream and j == pos[r], else 0      for n_old <= j < n_cls
+ *   l[r][j] = max(s, 0) - s * z + log1p(exp(-|s|))
+ *   old = (1/n) sum_r sum_{j < n_old} l       new = (1/n) sum_r sum_{n_old <= j < n_cls} l
+ *   loss_out[3] = {old + new, old, new}
+ *   dlogits[r][j] = (sig(s[r][j]) - z[r][j]) / n  for j < n_cls;  +0.0 for n_cls <= j < c
+ * = F.binary_cross_entropy_with_logits(logits[:, :n_cls], target, reduction='none').sum(1).mean() with the
+ * reference's target.  pos is int64 [n_stream]; a pos[r] below n_old is overwritten by the teacher's value, one
+ * outside [0, n_cls) sets no target.  Logit and teacher columns j >= n_cls and teacher columns j >= n_old are
+ * never read (a NaN there changes nothing).  sig(s) and sig(t) come from one function and are rounded before
+ * they are subtracted: a teacher that equals the logits bit for bit gives exactly 0 on the old columns.
+ * teacher == NULL requires n_old == 0 (iCaRL's first task).  dlogits may be NULL (losses only: the same three
+ * values).  One workgroup, one wave per row, element, row and cross-row sums in double and in a fixed order
+ * without atomics: two runs give the same bits.  A row of up to 256 columns is held in registers; a longer
+ * one takes a strided loop.  Ordered on `stream`, no host synchronisation.  OCL_ERR_ARG ("bce_distill: ...")
+ * before any launch, nothing written, for a null logits, pos or loss_out, n < 1, c < 1, n_stream outside
+ * [1, n], anything but 0 <= n_old <= n_cls <= c, n_old > 0 without a teacher, or a dlogits that overlaps
+ * logits, teacher or pos. */
+int ocl_bce_distill_fwd_bwd(const float* logits, const float* teacher, const int64_t* pos, int n, int n_stream, int c, int n_cls,
+                            int n_old, float* loss_out, float* dlogits, void* stream);
+
 /* ---- K7: supervised contrastive loss ---------------------------------------------------------------
  * SupConLoss.forward with contrast_mode='all' (utils/loss.py:19-96).  feat is VIEW-MAJOR
  * [n_views*bsz, dim] (= torch.cat(torch.unbind(features,1)), loss.py:56).  workspace: at least

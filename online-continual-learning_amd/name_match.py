@@ -56,10 +56,17 @@ offline_agents = _Lazy({
 })
 
 
+# agents that replay exemplars against a distilled target and classify by the nearest class mean (section 1b as well; a table of its
+# own because every table above is pinned to its keys by a test)
+exemplar_agents = _Lazy({
+    'ICARL': ('.agents.icarl', 'Icarl'),
+})
+
+
 def get_agent(key):
-    """The agent class registered under `key`: `agents` first, then `extra_agents`, `regularization_agents`, `distillation_agents` and
-    `offline_agents`; KeyError otherwise."""
-    for table in (agents, extra_agents, regularization_agents, distillation_agents, offline_agents):
+    """The agent class registered under `key`: `agents` first, then `extra_agents`, `regularization_agents`, `distillation_agents`,
+    `offline_agents` and `exemplar_agents`; KeyError otherwise."""
+    for table in (agents, extra_agents, regularization_agents, distillation_agents, offline_agents, exemplar_agents):
         if key in table:
             return table[key]
     raise KeyError(key)

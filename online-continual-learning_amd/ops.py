@@ -363,6 +363,47 @@ def ce_kd_blend(logits, y, teacher_logits, T, w_new, w_old, want_grad=True, dl_o
     return loss, dl
 
 
+# ---- K6c ---------------------------------------------------------------------------------------------
+def bce_distill(logits, teacher_logits, pos, n_stream, n_cls, n_old, want_grad=True, dl_out=None):
+    """(loss3, dlogits) of iCaRL's loss (agents/icarl.py:42-62) in one launch: the binary cross-entropy of logits[:, :n_cls] against the
+    target that is sigmoid(teacher_logits) on the columns below n_old and, on the columns from n_old to n_cls, the one-hot of `pos` for
+    the first n_stream rows and zero for the others (the memory rows), summed over the columns and averaged over the rows.
+    loss3 = [old + new, old, new] (the old and the new columns' parts); dlogits is the gradient of loss3[0], +0.0 in the columns from
+    n_cls on.  pos: int64 [n_stream], the target column of each stream row.  teacher_logits None (no teacher yet) requires n_old == 0.
+    Nothing is made contiguous or converted here: a tensor of another dtype, shape, layout or device is refused.  dl_out: a contiguous
+    float32 [n, c] tensor (e.g. a row block of a larger gradient buffer) that receives dlogits instead of a fresh one."""
+    def refuse(what, t, dtype, shape):
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise RuntimeError("bce_distill: %s must be a contiguous %s tensor of shape %s, got %s %s%s" % (
+                what, dtype, tuple(shape), getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ())),
+                "" if not torch.is_tensor(t) or t.is_contiguous() else " (not contiguous)"))
+
+    if not torch.is_tensor(logits) or logits.dim() != 2:
+        raise RuntimeError("bce_distill: logits must be a [n, c] tensor")
+    refuse("logits", logits, torch.float32, logits.shape)
+    n, c = logits.shape
+    n_stream, n_cls, n_old = int(n_stream), int(n_cls), int(n_old)
+    if not (1 <= n_stream <= n and 0 <= n_old <= n_cls <= c):
+        raise RuntimeError("bce_distill: n_stream=%d n_cls=%d n_old=%d with logits %s (1 <= n_stream <= n, 0 <= n_old <= n_cls <= c)"
+                           % (n_stream, n_cls, n_old, (n, c)))
+    refuse("pos", pos, torch.int64, (n_stream,))
+    if teacher_logits is not None:
+        refuse("teacher_logits", teacher_logits, torch.float32, (n, c))
+    elif n_old:
+        raise RuntimeError("bce_distill: n_old=%d without teacher_logits" % n_old)
+    if dl_out is not None:
+        refuse("dl_out", dl_out, torch.float32, (n, c))
+    for what, t in (("logits", logits), ("pos", pos), ("teacher_logits", teacher_logits), ("dl_out", dl_out)):
+        if t is not None and (not t.is_cuda or t.device != logits.device):
+            raise RuntimeError("bce_distill: %s is on %s; every tensor lives on the logits' GPU" % (what, t.device))
+    ffi.init()
+    loss = torch.empty(3, dtype=torch.float32, device=logits.device)
+    dl = dl_out if dl_out is not None else (torch.empty_like(logits) if want_grad else None)
+    ffi.check(ffi.lib().ocl_bce_distill_fwd_bwd(ffi.ptr(logits), ffi.ptr(teacher_logits), ffi.ptr(pos), n, n_stream, c, n_cls, n_old,
+                                                ffi.ptr(loss), ffi.ptr(dl), ffi.stream()), "bce_distill")
+    return loss, dl
+
+
 # ---- K7 ----------------------------------------------------------------------------------------------
 def supcon(feat_view_major, y, n_views, temperature, want_grad=True):
     """(loss, dfeat) for view-major features [n_views*bsz, dim] (utils/loss.py:19-96)."""

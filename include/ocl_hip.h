@@ -209,6 +209,23 @@ int ocl_ce_kd_blend_fwd_bwd(const float* logits, const int64_t* y, const float* 
 int ocl_bce_distill_fwd_bwd(const float* logits, const float* teacher, const int64_t* pos, int n, int n_stream, int c, int n_cls,
                             int n_old, float* loss_out, float* dlogits, void* stream);
 
+/* ---- K6d: per-row arg-max and group sum (evaluate()'s error analysis) -----------------------------------
+ * agents/base.py:179-203 and :217-218.  x is [n, c], row-major and contiguous.  Per row r, in ONE launch:
+ *   argmax_out[r] = the smallest column index among the row's maxima; a NaN compares as larger than everything
+ *                   and the first NaN wins (torch.max(x, 1) on the CPU); -0.0 and +0.0 are equal
+ *   sum_out[r]    = the sum in double of x[r][j] over the columns with col_group[j] == sel
+ * col_group is int32 [c]; NULL sums every column.  Columns outside the group are left out by a select, not
+ * multiplied by 0: a NaN or Inf there leaves the sum's bits alone; an empty group gives +0.0.  Either output
+ * may be NULL (not computed), not both; the one that is computed has the bits it has when both are.  Outputs
+ * may point into the middle of larger buffers.  One wave per row, four rows per workgroup; a row of up to 256
+ * columns is held in registers, a longer one takes a strided loop; lane l adds its columns l, l + 64, ... in
+ * order, then a shuffle tree: no atomics, two runs give the same bits, and a row's results depend neither on n
+ * nor on where in the grid it was computed.  Ordered on `stream`, no host synchronisation.  OCL_ERR_ARG
+ * ("row_argmax_groupsum: ...") before any launch, nothing written, for a null x, both outputs null, n < 1,
+ * c < 1, an output that overlaps x or col_group, or outputs that overlap each other. */
+int ocl_row_argmax_groupsum(const float* x, int n, int c, const int32_t* col_group, int sel, int64_t* argmax_out,
+                            double* sum_out, void* stream);
+
 /* ---- K7: supervised contrastive loss ---------------------------------------------------------------
  * SupConLoss.forward with contrast_mode='all' (utils/loss.py:19-96).  feat is VIEW-MAJOR
  * [n_views*bsz, dim] (= torch.cat(torch.unbind(features,1)), loss.py:56).  workspace: at least

@@ -6,6 +6,7 @@ parameter-snapshot teacher (kd_manager.py)."""
 from abc import abstractmethod
 import abc
 import copy
+import pickle
 
 import numpy as np
 import torch
@@ -14,6 +15,7 @@ from .. import ops
 from .. import debug
 from ..loss import SupConLoss, cross_entropy_mean, cross_entropy_segmented_mean, unit_gradient
 from ..kd_manager import KdManager
+from ..error_analysis import ErrorAnalysis, TorchErrorAnalysis
 from ..utils import maybe_cuda, AverageMeter
 
 
@@ -38,10 +40,24 @@ class ContinualLearner(torch.nn.Module, metaclass=abc.ABCMeta):
         self.lbl_inv_map = {}
         self.class_task_map = {}
         self.kd_manager = KdManager()
-        if getattr(params, 'error_analysis', False):
-            raise NotImplementedError("error_analysis is outside the HIP hot path")
+        # agents/base.py:33-39: what evaluate() appends to with params.error_analysis (error_analysis.py)
+        self.error_list = []
+        self.new_class_score = []
+        self.old_class_score = []
+        self.fc_norm_new = []
+        self.fc_norm_old = []
+        self.bias_norm_new = []
+        self.bias_norm_old = []
+        if getattr(params, 'error_analysis', False) and self._predicts_by_ncm():
+            raise NotImplementedError(
+                "error_analysis with nearest-class-mean prediction (ncm_trick, or agent ICARL, SCR or SCP) is not defined: the reference's "
+                "branch reads the `logits` its NCM path never computes, and compares indices into old_labels with class labels")
 
     _gc_frozen = False
+    _force_torch_error_analysis = False    # the error analysis by per-tensor torch operations and host reads (the comparator of the fused path)
+
+    def _predicts_by_ncm(self):
+        return self.params.trick['ncm_trick'] or self.params.agent in ['ICARL', 'SCR', 'SCP']
 
     @classmethod
     def _freeze_long_lived_objects(cls):
@@ -214,7 +230,7 @@ class ContinualLearner(torch.nn.Module, metaclass=abc.ABCMeta):
         eval-mode BatchNorm makes the batched extraction below numerically equivalent per sample."""
         self.model.eval()
         acc_array = np.zeros(len(test_loaders))
-        use_ncm = self.params.trick['ncm_trick'] or self.params.agent in ['ICARL', 'SCR', 'SCP']
+        use_ncm = self._predicts_by_ncm()
         if use_ncm:
             buffer_filled = self.buffer.current_index
             dev = self.buffer.buffer_img.device
@@ -238,15 +254,31 @@ class ContinualLearner(torch.nn.Module, metaclass=abc.ABCMeta):
                         mu_y = torch.normal(0, 1, size=(1, feats.shape[1])).squeeze()
                         mu_y = mu_y / mu_y.norm()
                         means[ci] = mu_y.to(dev)
+        ea = None
+        if getattr(self.params, 'error_analysis', False):
+            # agents/base.py:144-153: counters, score meters and confusion lists start afresh in every call
+            ea = TorchErrorAnalysis() if self._force_torch_error_analysis else ErrorAnalysis()
+            ea.begin(self.old_labels, self.new_labels_zombie, self.class_task_map, self.task_seen, self.model.linear.out_features,
+                     self.model.linear.weight.device)
         with torch.no_grad():
             for task, test_loader in enumerate(test_loaders):
                 acc = AverageMeter()
                 correct = []
                 sizes = []
                 seen_idx, seen_pred = [], []
+                if ea is not None:
+                    ea.begin_loader(task, self._loader_rows(test_loader))
                 for i, (batch_x, batch_y) in enumerate(test_loader):
                     batch_x = maybe_cuda(batch_x, self.cuda)
                     batch_y = maybe_cuda(batch_y, self.cuda)
+                    if ea is not None:
+                        # the softmax branch through error_analysis.py: one launch for the batch, read with the loader's one copy below
+                        logits = self.model.forward(batch_x)
+                        pred_label = ea.batch(logits, self._host_labels(batch_y))
+                        if debug.on():
+                            seen_idx.append(np.asarray(test_loader.last_index_host).copy())
+                            seen_pred.append(pred_label.cpu().numpy())
+                        continue
                     if use_ncm:
                         feature = self.model.features_batched(batch_x)  # (batch_size, feature_size)
                         pred = ops.ncm_predict(feature, means)
@@ -262,10 +294,44 @@ class ContinualLearner(torch.nn.Module, metaclass=abc.ABCMeta):
                 if debug.on():
                     debug.emit("evaluate", task=task, index=np.concatenate(seen_idx) if seen_idx else np.zeros(0, dtype=np.int64),
                                pred=np.concatenate(seen_pred) if seen_pred else np.zeros(0, dtype=np.int64))
-                if correct:
+                if ea is not None:
+                    for c, n in ea.end_loader():                      # one sync per task loader
+                        acc.update(c / n, n)
+                elif correct:
                     correct_h = torch.stack(correct).cpu().tolist()   # one sync per task loader
                     for c, n in zip(correct_h, sizes):
                         acc.update(c / n, n)
                 acc_array[task] = acc.avg()
         print(acc_array)
+        if ea is not None:
+            self._report_error_analysis(ea)
         return acc_array
+
+    @staticmethod
+    def _loader_rows(test_loader):
+        """The number of rows a test loader will yield (the length of the error analysis' device tables)."""
+        y_host = getattr(test_loader, 'y_host', None)
+        return len(y_host) if y_host is not None else len(test_loader.dataset)
+
+    def _report_error_analysis(self, ea):
+        """agents/base.py:209-226: the appends, the prints and the `confusion` file of the reference, in its order."""
+        no, nn, oo, on = ea.error_tuple()
+        self.error_list.append((no, nn, oo, on))
+        self.new_class_score.append(ea.new_class_score.avg())
+        self.old_class_score.append(ea.old_class_score.avg())
+        print("no ratio: {}\non ratio: {}".format(no / (no + nn + 0.1), on / (oo + on + 0.1)))
+        print(self.error_list)
+        print(self.new_class_score)
+        print(self.old_class_score)
+        norms = ea.end(self.model.linear)
+        self.fc_norm_new.append(norms['fc_norm_new'])
+        self.fc_norm_old.append(norms['fc_norm_old'])
+        self.bias_norm_new.append(norms['bias_norm_new'])
+        self.bias_norm_old.append(norms['bias_norm_old'])
+        print(self.fc_norm_old)
+        print(self.fc_norm_new)
+        print(self.bias_norm_old)
+        print(self.bias_norm_new)
+        self.confusion = [ea.correct_lb, ea.predict_lb]
+        with open('confusion', 'wb') as fp:
+            pickle.dump(self.confusion, fp)

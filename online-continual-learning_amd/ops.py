@@ -404,6 +404,46 @@ def bce_distill(logits, teacher_logits, pos, n_stream, n_cls, n_old, want_grad=T
     return loss, dl
 
 
+# ---- K6d ---------------------------------------------------------------------------------------------
+def row_argmax_groupsum(x, col_group=None, sel=0, want_argmax=True, want_sum=True, argmax_out=None, sum_out=None):
+    """(argmax int64 [n] | None, sums float64 [n] | None) of the rows of x [n, c] in one launch: the smallest column index among each row's
+    maxima (a NaN is larger than everything and the first NaN wins, -0.0 equals +0.0: torch.max(x, 1) on the CPU), and the sum in double
+    of the row's columns j with col_group[j] == sel (col_group int32 [c]; None sums every column; the other columns are not looked at,
+    an empty group gives +0.0).  Nothing is made contiguous or converted here: a tensor of another dtype, shape, layout or device is
+    refused.  argmax_out / sum_out: contiguous int64 / float64 [n] tensors (e.g. a row block of a loader-long table) that receive the
+    results instead of fresh ones; giving one asks for that result."""
+    def refuse(what, t, dtype, shape):
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise RuntimeError("row_argmax_groupsum: %s must be a contiguous %s tensor of shape %s, got %s %s%s" % (
+                what, dtype, tuple(shape), getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ())),
+                "" if not torch.is_tensor(t) or t.is_contiguous() else " (not contiguous)"))
+
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise RuntimeError("row_argmax_groupsum: x must be a [n, c] tensor")
+    refuse("x", x, torch.float32, x.shape)
+    n, c = x.shape
+    if n < 1 or c < 1:
+        raise RuntimeError("row_argmax_groupsum: x is %s (n and c must be >= 1)" % ((n, c),))
+    want_argmax, want_sum = bool(want_argmax) or argmax_out is not None, bool(want_sum) or sum_out is not None
+    if not (want_argmax or want_sum):
+        raise RuntimeError("row_argmax_groupsum: neither the arg-max nor the sums are asked for")
+    if col_group is not None:
+        refuse("col_group", col_group, torch.int32, (c,))
+    if argmax_out is not None:
+        refuse("argmax_out", argmax_out, torch.int64, (n,))
+    if sum_out is not None:
+        refuse("sum_out", sum_out, torch.float64, (n,))
+    for what, t in (("x", x), ("col_group", col_group), ("argmax_out", argmax_out), ("sum_out", sum_out)):
+        if t is not None and (not t.is_cuda or t.device != x.device):
+            raise RuntimeError("row_argmax_groupsum: %s is on %s; every tensor lives on x's GPU" % (what, t.device))
+    ffi.init()
+    am = argmax_out if argmax_out is not None else (torch.empty(n, dtype=torch.int64, device=x.device) if want_argmax else None)
+    sm = sum_out if sum_out is not None else (torch.empty(n, dtype=torch.float64, device=x.device) if want_sum else None)
+    ffi.check(ffi.lib().ocl_row_argmax_groupsum(ffi.ptr(x), n, c, ffi.ptr(col_group), int(sel), ffi.ptr(am), ffi.ptr(sm), ffi.stream()),
+              "row_argmax_groupsum")
+    return am, sm
+
+
 # ---- K7 ----------------------------------------------------------------------------------------------
 def supcon(feat_view_major, y, n_views, temperature, want_grad=True):
     """(loss, dfeat) for view-major features [n_views*bsz, dim] (utils/loss.py:19-96)."""

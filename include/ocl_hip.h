@@ -62,6 +62,14 @@ int ocl_upload(const void* host, int64_t nbytes, void* dev, void* stream);
  * tensor and writes CHW fp32 / 255. */
 int ocl_gather_u8_hwc_to_f32_chw(const uint8_t* src, const int64_t* idx, int64_t n, int h, int w,
                                  int c, float* dst, void* stream);
+/* The same for a task whose images are already float (the new-instance streams of continuum/non_stationary.py hand
+ * over HWC arrays divided by 255): dataset_transform.__getitem__ on a non-uint8 array is ToTensor's transpose HWC ->
+ * CHW and .float(), nothing else.  The float32 rounding is done once per task on the host; this gathers n HWC float32
+ * images by index from the device-resident task and writes them CHW, bit for bit (NaN payloads, -0.0 and denormals
+ * included).  16-byte loads when h*w*c is a multiple of 4, src is 16-byte aligned and c <= 16; 4-byte loads otherwise.
+ * src and dst must be 4-byte aligned. */
+int ocl_gather_f32_hwc_to_f32_chw(const float* src, const int64_t* idx, int64_t n, int h, int w, int c,
+                                  float* dst, void* stream);
 
 /* ---- K8: SGD -------------------------------------------------------------------------------------
  * torch.optim.SGD.step with momentum 0 (utils/setup_elements.py:73-75): p <- p - lr*(g + wd*p).

@@ -131,6 +131,23 @@ def gather_u8_images(task_u8_nhwc, idx):
     return out
 
 
+def gather_f32_images(task_f32_nhwc, idx):
+    """ToTensor() + .float() of task_f32_nhwc[idx] for a task that is float already (a new-instance stream): float32 [N,H,W,C] ->
+    float32 [n,C,H,W], a transpose that keeps every bit.  The task may be a view whose rows are contiguous (a slice along N)."""
+    ffi.init()
+    idx = _i64(idx)
+    n = idx.numel()
+    if task_f32_nhwc.dtype != torch.float32 or not task_f32_nhwc.is_cuda or task_f32_nhwc.dim() != 4:
+        raise RuntimeError("gather_f32_images: expected a float32 [N,H,W,C] tensor on the GPU, got %s %s on %s"
+                           % (task_f32_nhwc.dtype, tuple(task_f32_nhwc.shape), task_f32_nhwc.device))
+    _, h, w, c = task_f32_nhwc.shape
+    out = torch.empty((n, c, h, w), dtype=torch.float32, device=task_f32_nhwc.device)
+    if n:
+        ffi.check(ffi.lib().ocl_gather_f32_hwc_to_f32_chw(ffi.ptr(task_f32_nhwc), ffi.ptr(idx), n, h, w, c, ffi.ptr(out),
+                                                          ffi.stream()), "gather_f32")
+    return out
+
+
 # ---- K8 ----------------------------------------------------------------------------------------------
 def sgd_step(params_flat, grads_flat, lr, weight_decay=0.0, grad_scale=1.0, out=None):
     ffi.init()

@@ -407,6 +407,12 @@ class _EngineMixin:
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
 
+def _default_max_batch(h, w):
+    """The engine's batch capacity when `model.max_batch` is not set: the workspace grows with max_batch * h * w, and the default
+    --test_batch (128) must fit one forward at every input size of the reference (128x128 included)."""
+    return 512 if h * w <= 32 * 32 else 256 if h * w <= 84 * 84 else 128
+
+
 class ResNet(nn.Module, _EngineMixin):
     """models/resnet.py:69-109 with BasicBlock; `Reduced_ResNet18` = ResNet([2,2,2,2], nclasses, nf=20)."""
 
@@ -436,7 +442,7 @@ class ResNet(nn.Module, _EngineMixin):
 
     def _engine_desc(self):
         h, w = self.in_hw
-        mb = self.max_batch or (512 if h * w <= 32 * 32 else 256)
+        mb = self.max_batch or _default_max_batch(h, w)
         return ffi.NetDesc(h, w, self.nf, self.linear.out_features, 0, 0, mb, self.n_slots + 1)   # + the scratch slot
 
     def features(self, x):
@@ -478,7 +484,7 @@ class SupConResNet(nn.Module, _EngineMixin):
     def _engine_desc(self):
         h, w = self.encoder.in_hw
         kind = {'mlp': 1, 'linear': 2, 'None': 3}[self.head_kind]
-        mb = self.max_batch or (512 if h * w <= 32 * 32 else 256)
+        mb = self.max_batch or _default_max_batch(h, w)
         return ffi.NetDesc(h, w, self.encoder.nf, 100, kind, self.feat_dim, mb, self.n_slots + 1)   # + the scratch slot
 
     def forward(self, x):

@@ -34,13 +34,14 @@ def setup_architecture(params):
         if params.data == 'mini_imagenet':
             return SupConResNet(640, head=params.head, in_hw=hw)
         return SupConResNet(head=params.head, in_hw=hw)
-    if params.data in ('cifar100', 'cifar10'):
+    if params.data in ('cifar100', 'cifar10', 'openloris'):
+        # openloris: 50x50 -> a 7x7 final map that avg_pool2d(4) crops to one window: the 160-wide classifier the net is born with
         return Reduced_ResNet18(nclass, in_hw=hw)
-    if params.data == 'mini_imagenet':
-        model = Reduced_ResNet18(nclass, in_hw=hw)
-        model.linear = nn.Linear(640, nclass, bias=True)
-        return model
-    raise NotImplementedError("dataset %r is outside the BASELINE configs of the HIP hot path" % (params.data,))
+    # core50 (128x128 -> a 4x4 pooled map, 2560 features) and mini_imagenet (84x84 -> 2x2, 640): the classifier is re-created
+    # (a second RNG draw, as in the reference)
+    model = Reduced_ResNet18(nclass, in_hw=hw)
+    model.linear = nn.Linear(2560 if params.data == 'core50' else 640, nclass, bias=True)
+    return model
 
 
 def setup_opt(optimizer, model, lr, wd):

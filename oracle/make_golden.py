@@ -17,7 +17,7 @@ sys.path.insert(0, ROOT)
 
 from oracle import ref_import as R  # noqa: E402
 from oracle import ocl_oracle as O  # noqa: E402
-from oracle.synth import make_stream, seed_all, digest_state, STEP_CASES, case_params  # noqa: E402
+from oracle.synth import make_stream, seed_all, digest_state, digest_nbt, digest_rng, STEP_CASES, case_params  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 
@@ -381,7 +381,7 @@ def run_reference_case(name):
                          buf_label=agent.buffer.buffer_label.numpy().copy(),
                          buf_rowsum=agent.buffer.buffer_img.double().sum(dim=(1, 2, 3)).numpy(),
                          counters=np.array([agent.buffer.current_index, agent.buffer.n_seen_so_far], dtype=np.int64),
-                         state=digest_state(model.state_dict())))
+                         state=digest_state(model.state_dict()), nbt=digest_nbt(model.state_dict()), rng=digest_rng()))
     return recs
 
 
@@ -399,7 +399,7 @@ def run_oracle_case(name, sort_fn):
             recs.append(dict(acc=np.asarray(acc, dtype=np.float64), buf_label=ag.buf.label.numpy().copy(),
                              buf_rowsum=ag.buf.img.double().sum(dim=(1, 2, 3)).numpy(),
                              counters=np.array([ag.buf.current_index, ag.buf.n_seen_so_far], dtype=np.int64),
-                             state=digest_state(ag.state_dict())))
+                             state=digest_state(ag.state_dict()), nbt=digest_nbt(ag.state_dict()), rng=digest_rng()))
     finally:
         O.ARGSORT_DESC = O.argsort_desc_stable
     return recs

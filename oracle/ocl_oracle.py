@@ -296,7 +296,7 @@ def sgd_step(state, names, lr, wd=0.0):
                 continue
             g = p.grad
             if wd != 0:
-                g = g + wd * p
+                g = g.add(p, alpha=wd)      # torch.optim.SGD's own statement: bit-equal to it, which g + wd * p is not
             p.add_(g, alpha=-lr)
 
 
@@ -578,8 +578,9 @@ def _retrieve_indices(buf, params, retrieve, batch_y, tracker, warmup):
     return random_retrieve_indices(buf, params["eps_mem_batch"])
 
 
-def scr_step(state, names, buf, batch_x, batch_y, params, aug=identity_aug, retrieve="random", tracker=None, warmup=4):
-    """agents/scr.py:40-63 for ONE iteration. Returns (loss or None, retrieved indices, written slots)."""
+def scr_step(state, names, buf, batch_x, batch_y, params, aug=identity_aug, retrieve="random", tracker=None, warmup=4, update=True):
+    """agents/scr.py:40-63 for ONE iteration. Returns (loss or None, retrieved indices, written slots).  update=False is the train
+    part alone (:47-60, one pass of the mem_iters loop; slots None): the buffer update of :63 is `reservoir_update`."""
     net = OracleNet(state, head=params.get("head", "mlp"), training=True)
     idx = _retrieve_indices(buf, params, retrieve, batch_y, tracker, warmup)
     loss = None
@@ -591,13 +592,21 @@ def scr_step(state, names, buf, batch_x, batch_y, params, aug=identity_aug, retr
         loss = supcon_loss(feats, cy, params["temp"])
         zero_grad(state, names)
         loss.backward()
-        sgd_step(state, names, params["lr"])
-    slots = reservoir_update(buf, batch_x, batch_y, tracker=tracker)
+        sgd_step(state, names, params["lr"], params.get("wd", 0.0))
+    slots = reservoir_update(buf, batch_x, batch_y, tracker=tracker) if update else None
     return (None if loss is None else float(loss.detach())), idx, slots
 
 
-def er_step(state, names, buf, batch_x, batch_y, params, retrieve="random", gss=None, tracker=None, warmup=4, kd=None):
+def er_update(state, names, buf, batch_x, batch_y, gss=None, tracker=None):
+    """agents/exp_replay.py:92 (buffer.update, once per stream batch, after the mem_iters loop): reservoir or GSS."""
+    if gss is not None:
+        return {"gss": gss_update(gss, state, names, buf, batch_x, batch_y)}
+    return {"slots": reservoir_update(buf, batch_x, batch_y, tracker=tracker)}
+
+
+def er_step(state, names, buf, batch_x, batch_y, params, retrieve="random", gss=None, tracker=None, warmup=4, kd=None, update=True):
     """agents/exp_replay.py:34-92 for ONE iteration with random / MIR / match retrieval and reservoir or GSS update.
+    update=False is the train part alone (:40-89, one pass of the mem_iters loop); the update part is `er_update`.
     kd(loss, logits, x) -> loss: the KD tricks' blend of the cross-entropy with the distillation loss (exp_replay.py:42-47, :64-69)."""
     net = OracleNet(state, head=None, training=True)
     logits = net.forward(batch_x)
@@ -642,16 +651,15 @@ def er_step(state, names, buf, batch_x, batch_y, params, retrieve="random", gss=
             loss_mem = kd(loss_mem, mem_logits, buf.img[idx])
         loss_mem.backward()
         info["loss_mem"] = float(loss_mem.detach())
-    sgd_step(state, names, params["lr"])
-    if gss is not None:
-        info["gss"] = gss_update(gss, state, names, buf, batch_x, batch_y)
-    else:
-        info["slots"] = reservoir_update(buf, batch_x, batch_y, tracker=tracker)
+    sgd_step(state, names, params["lr"], params.get("wd", 0.0))
+    if update:
+        info.update(er_update(state, names, buf, batch_x, batch_y, gss=gss, tracker=tracker))
     return info
 
 
-def aser_er_step(state, names, buf, cache, batch_x, batch_y, params):
-    """agents/exp_replay.py:34-92 with --retrieve ASER --update ASER (combined-batch branch :79-87)."""
+def aser_er_step(state, names, buf, cache, batch_x, batch_y, params, update=True):
+    """agents/exp_replay.py:34-92 with --retrieve ASER --update ASER (combined-batch branch :79-87).  update=False is the train part
+    alone (one pass of the mem_iters loop); the update part (:92) is `aser_update` on a train-mode net over the same state."""
     net = OracleNet(state, head=None, training=True)
     info = {}
     loss = ce_mean(net.forward(batch_x), batch_y)
@@ -669,9 +677,10 @@ def aser_er_step(state, names, buf, cache, batch_x, batch_y, params):
     cx, cy = torch.cat((mem_x, batch_x)), torch.cat((mem_y, batch_y))
     lc = ce_mean(net.forward(cx), cy)
     lc.backward()
-    sgd_step(state, names, params["lr"])
+    sgd_step(state, names, params["lr"], params.get("wd", 0.0))
     info["loss"] = float(lc.detach())
-    info["upd"] = aser_update(net, buf, cache, batch_x, batch_y, params)
+    if update:
+        info["upd"] = aser_update(net, buf, cache, batch_x, batch_y, params)
     return info
 
 
@@ -720,7 +729,7 @@ def review_epoch(state, names, buf, params, agent, aug=identity_aug):
             for k in names:
                 if state[k].grad is not None:
                     state[k].grad.copy_(state[k].grad.clone() / 10.)
-        sgd_step(state, names, params["lr"])
+        sgd_step(state, names, params["lr"], params.get("wd", 0.0))
         out.append((idx.numpy().copy(), float(loss.detach())))
     return out
 
@@ -888,7 +897,8 @@ def to_tensor(x_u8):
 class OracleAgent(object):
     """ONE run of agents/exp_replay.py / agents/scr.py + agents/base.py on CPU, built from the step functions above.
     `cfg` is an oracle.synth.STEP_CASES-style dict; cfg["trick"] may switch on review_trick / ncm_trick (agents/base.py:62-88,
-    :121)."""
+    :121); cfg["epoch"], cfg["mem_iters"], cfg["batch"], cfg["weight_decay"], cfg["learning_rate"] as the reference's parameters of
+    those names.  The log holds one entry per stream batch; with mem_iters > 1 the train part's fields are per-j lists."""
 
     def __init__(self, cfg, aug=identity_aug):
         self.cfg = dict(cfg)
@@ -901,13 +911,16 @@ class OracleAgent(object):
         self.buf = OracleBuffer(cfg["mem_size"], (3, hw, hw))
         self.cache = ClassCache()
         self.n_classes = {"cifar100": 100, "cifar10": 10, "mini_imagenet": 100}[self.data]
-        self.p = dict(eps_mem_batch=cfg["eps_mem_batch"], temp=cfg.get("temp", 0.07), lr=cfg.get("lr", 0.1), head=self.head,
+        self.p = dict(eps_mem_batch=cfg["eps_mem_batch"], temp=cfg.get("temp", 0.07), lr=cfg.get("learning_rate", cfg.get("lr", 0.1)), head=self.head,
                       subsample=cfg.get("subsample", 50), k=cfg.get("k", 3), n_smp_cls=cfg.get("n_smp_cls", 1.5),
-                      aser_type=cfg.get("aser_type", "asvm"), mem_size=cfg["mem_size"], n_classes=self.n_classes)
+                      aser_type=cfg.get("aser_type", "asvm"), mem_size=cfg["mem_size"], n_classes=self.n_classes,
+                      wd=cfg.get("weight_decay", 0.0))
         self.trick = dict(cfg.get("trick", {}))
         self.old_labels = []
         self.aug = aug
         self.batch = cfg.get("batch", 10)
+        self.epoch = cfg.get("epoch", 1)
+        self.mem_iters = cfg.get("mem_iters", 1)
         self.log = []
         self.review_log = []
         self.gss = GssState(cfg) if cfg.get("update") == "GSS" else None
@@ -936,17 +949,38 @@ class OracleAgent(object):
         xs = to_tensor(x_u8)
         ys = torch.from_numpy(np.asarray(y)).long()
         loader = torch.utils.data.DataLoader(_Idx(len(ys)), batch_size=self.batch, shuffle=True, drop_last=True)
-        for idx in loader:
-            bx, by = xs[idx], ys[idx]
-            if self.agent == "SCR":
-                self.log.append(scr_step(self.state, self.names, self.buf, bx, by, self.p, self.aug, retrieve=self.cfg.get("retrieve", "random"),
-                                         tracker=self.tracker, warmup=self.cfg.get("warmup", 4)))
-            elif self.cfg["retrieve"] == "ASER" or self.cfg["update"] == "ASER":
-                self.log.append(aser_er_step(self.state, self.names, self.buf, self.cache, bx, by, self.p))
-            else:
-                kd = self._kd_mix if (self.trick.get("kd_trick") or self.trick.get("kd_trick_star")) else None
-                self.log.append(er_step(self.state, self.names, self.buf, bx, by, self.p, self.cfg["retrieve"], gss=self.gss,
-                                        tracker=self.tracker, warmup=self.cfg.get("warmup", 4), kd=kd))
+        aser = self.agent != "SCR" and (self.cfg["retrieve"] == "ASER" or self.cfg["update"] == "ASER")
+        kd = self._kd_mix if (self.trick.get("kd_trick") or self.trick.get("kd_trick_star")) else None
+        warmup = self.cfg.get("warmup", 4)
+        for ep in range(self.epoch):                                           # exp_replay.py:33 / scr.py:39: a fresh permutation per epoch
+            for idx in loader:
+                bx, by = xs[idx], ys[idx]
+                parts = []
+                for j in range(self.mem_iters):                                # exp_replay.py:39 / scr.py:47: the train part
+                    if self.agent == "SCR":
+                        parts.append(scr_step(self.state, self.names, self.buf, bx, by, self.p, self.aug, retrieve=self.cfg.get("retrieve", "random"),
+                                              tracker=self.tracker, warmup=warmup, update=False))
+                    elif aser:
+                        parts.append(aser_er_step(self.state, self.names, self.buf, self.cache, bx, by, self.p, update=False))
+                    else:
+                        parts.append(er_step(self.state, self.names, self.buf, bx, by, self.p, self.cfg["retrieve"], gss=self.gss,
+                                             tracker=self.tracker, warmup=warmup, kd=kd, update=False))
+                if self.agent == "SCR":                                        # exp_replay.py:92 / scr.py:63: the buffer update, once per batch
+                    slots = reservoir_update(self.buf, bx, by, tracker=self.tracker)
+                    self.log.append((parts[0][0], parts[0][1], slots) if self.mem_iters == 1 else
+                                    ([p[0] for p in parts], [p[1] for p in parts], slots))
+                    continue
+                if aser:
+                    upd = {"upd": aser_update(OracleNet(self.state, head=None, training=True), self.buf, self.cache, bx, by, self.p)}
+                else:
+                    upd = er_update(self.state, self.names, self.buf, bx, by, gss=self.gss, tracker=self.tracker)
+                if self.mem_iters == 1:
+                    self.log.append(dict(parts[0], **upd))
+                else:                                                          # per-j lists (None where a pass has no such entry)
+                    keys = []
+                    for p in parts:
+                        keys += [k for k in p if k not in keys]
+                    self.log.append(dict({k: [p.get(k) for p in parts] for k in keys}, **upd))
         self.after_train(new)
 
     def after_train(self, new):

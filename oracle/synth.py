@@ -54,12 +54,30 @@ STEP_CASES = {
                       tasks=[[0, 1], [2, 3], [4, 5]], n_train=30, n_test=20, trick=dict(kd_trick=True, kd_trick_star=True)),
     "er_gss": dict(agent="ER", retrieve="random", update="GSS", data="cifar10", mem_size=20, eps_mem_batch=10, seed=9,
                    tasks=[[0], [1]], n_train=30, n_test=20, gss_mem_strength=3, gss_batch_size=5, free_run_gpu=False),
+    # The outer loops of the agents (agents/exp_replay.py:33-92, agents/scr.py:39-63): two epochs (a fresh loader permutation each) and
+    # two memory iterations per stream batch (retrieve + step twice, ONE buffer update after them)
+    "er_loops": dict(agent="ER", retrieve="random", update="random", data="cifar10", mem_size=50, eps_mem_batch=10, seed=13,
+                     tasks=[[0, 1], [2, 3]], n_train=30, n_test=20, batch=10, epoch=2, mem_iters=2),
+    # batch 8 against a retrieval of 12 from a memory that is full from the first task on: never the merged two-group pass; 60 samples
+    # per task -> 7 batches, 4 samples dropped (drop_last); weight decay and a learning rate of its own on the way to the SGD statement
+    "er_uneven": dict(agent="ER", retrieve="random", update="random", data="cifar10", mem_size=50, eps_mem_batch=12, seed=14,
+                      tasks=[[0, 1], [2, 3]], n_train=30, n_test=20, batch=8, epoch=1, mem_iters=2, weight_decay=1e-4, learning_rate=0.05),
+    "scr_loops": dict(agent="SCR", retrieve="random", update="random", data="cifar100", mem_size=60, eps_mem_batch=20, seed=15,
+                      tasks=[[3, 17], [40, 41]], n_train=25, n_test=20, temp=0.07, head="mlp", epoch=2, mem_iters=2),
+    # MIR: the virtual step of pass j reads the gradient of the batch pass of the same j (seed chosen tie-free, as for mir_c10)
+    "mir_loops": dict(agent="ER", retrieve="MIR", update="random", data="cifar10", mem_size=40, eps_mem_batch=10, seed=18,
+                      tasks=[[0, 1, 2, 3, 4], [5, 6, 7, 8, 9]], n_train=10, n_test=8, subsample=20, epoch=2, mem_iters=2),
+    # ER + ASER (the pipelined loop of the engine): Shapley totals tie as in aser_c100, so this is pinned to the oracle only
+    "aser_loops": dict(agent="ER", retrieve="ASER", update="ASER", data="cifar100", mem_size=40, eps_mem_batch=10, seed=17,
+                       tasks=[list(range(10))], n_train=6, n_test=4, k=3, n_smp_cls=1.5, aser_type="asvm", epoch=2, mem_iters=2,
+                       golden=False),
 }
 
 
 def case_params(cfg):
     keys = ("agent", "retrieve", "update", "data", "mem_size", "eps_mem_batch", "seed", "temp", "head", "k", "n_smp_cls", "aser_type",
-            "subsample", "buffer_tracker", "warmup", "gss_mem_strength", "gss_batch_size")
+            "subsample", "buffer_tracker", "warmup", "gss_mem_strength", "gss_batch_size", "epoch", "mem_iters", "batch", "weight_decay",
+            "learning_rate")
     p = {k: cfg[k] for k in keys if k in cfg}
     p["num_tasks"] = len(cfg["tasks"])
     if "trick" in cfg:
@@ -105,6 +123,19 @@ def digest_state(state_dict):
             d = v.detach().double().cpu().reshape(-1)
             rows.append([float(d.sum()), float(d.norm()), float(d[0])])
     return np.array(rows, dtype=np.float64)
+
+
+def digest_nbt(state_dict):
+    """int64 [n_batchnorm]: num_batches_tracked of every BatchNorm in state_dict order -- the exact count of train-mode forwards."""
+    return np.array([int(v) for k, v in state_dict.items() if k.endswith("num_batches_tracked")], dtype=np.int64)
+
+
+def digest_rng():
+    """int64 [3]: CRC-32 of torch's CPU generator state, CRC-32 of numpy's global Mersenne-Twister key, and its position."""
+    import zlib
+    st = np.random.get_state()
+    return np.array([zlib.crc32(torch.get_rng_state().numpy().tobytes()), zlib.crc32(np.ascontiguousarray(st[1]).tobytes()), int(st[2])],
+                    dtype=np.int64)
 
 
 def throughput_stream(data, n_classes_per_task, n_tasks, n_per_class, seed):

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Build container only (reference tree present): records tests/golden/agem.npz from the REAL reference agent (agents/agem.py) on the
-case `agem_c10` of tests/agem_ref.py.
+cases `agem_c10` and `agem_loops` (epoch 2, mem_iters 2) of tests/agem_ref.py.
 
 The reference runs twice (determinism at one thread); the restatement tests/agem_ref.py::agem_step runs over the same stream and every
 recorded array must be bit-equal to the reference's, otherwise nothing is written.  Per task: acc, buf_label, buf_rowsum, counters
-and the digest_state rows -- what oracle/make_golden.py records for its step cases.
+and the digest_state rows -- what oracle/make_golden.py records for its step cases; agem_loops also num_batches_tracked (nbt).
 
     python scripts/make_agem_golden.py
 """
@@ -21,7 +21,7 @@ from oracle import ref_import as R                                    # noqa: E4
 from oracle.synth import case_params, make_stream, seed_all          # noqa: E402
 import agem_ref                                                       # noqa: E402
 
-NAME = "agem_c10"
+CASES = (("agem_c10", agem_ref.AGEM_CASE, agem_ref.GOLDEN_KEYS), ("agem_loops", agem_ref.AGEM_LOOPS_CASE, agem_ref.LOOPS_KEYS))
 
 
 def run_reference_case(cfg, tasks_only=None):
@@ -47,20 +47,21 @@ def run_reference_case(cfg, tasks_only=None):
 def main():
     assert R.available(), "reference tree not found"
     torch.set_num_threads(1)
-    cfg = agem_ref.AGEM_CASE
-    ref, ref2 = run_reference_case(cfg), run_reference_case(cfg)
-    mine, ag = agem_ref.run_oracle_case(cfg)
     out = {}
-    for t, (a, b, c) in enumerate(zip(ref, ref2, mine)):
-        for k in agem_ref.GOLDEN_KEYS:
-            assert np.array_equal(a[k], b[k]), "the reference is not deterministic: task %d %s" % (t, k)
-            assert np.array_equal(a[k], c[k]), "agem_step != reference: task %d %s" % (t, k)
-            out["%s_t%d_%s" % (NAME, t, k)] = a[k]
-    out[NAME + "_ntasks"] = np.int64(len(ref))
-    seen = [e for e in ag.log if e["cos"] is not None]
-    print("%s: %d iterations, %d see memory, %d project, min |cos| %.4f, acc %s" % (
-        NAME, len(ag.log), len(seen), sum(e["projected"] for e in seen), min(abs(e["cos"]) for e in seen),
-        [np.round(r["acc"], 3).tolist() for r in ref]))
+    for name, cfg, keys in CASES:
+        ref, ref2 = run_reference_case(cfg), run_reference_case(cfg)
+        mine, ag = agem_ref.run_oracle_case(cfg)
+        for t, (a, b, c) in enumerate(zip(ref, ref2, mine)):
+            for k in keys:
+                assert np.array_equal(a[k], b[k]), "the reference is not deterministic: %s task %d %s" % (name, t, k)
+                assert np.array_equal(a[k], c[k]), "agem_step != reference: %s task %d %s" % (name, t, k)
+                out["%s_t%d_%s" % (name, t, k)] = a[k]
+        out[name + "_ntasks"] = np.int64(len(ref))
+        steps = ag.log if cfg.get("mem_iters", 1) == 1 else [dict(cos=c, projected=p) for e in ag.log for c, p in zip(e["cos"], e["projected"])]
+        seen = [e for e in steps if e["cos"] is not None]
+        print("%s: %d steps, %d see memory, %d project, min |cos| %.4f, acc %s" % (
+            name, len(steps), len(seen), sum(e["projected"] for e in seen), min(abs(e["cos"]) for e in seen),
+            [np.round(r["acc"], 3).tolist() for r in ref]))
     path = os.path.join(ROOT, "tests", "golden", "agem.npz")
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path), "bytes")

@@ -15,6 +15,10 @@ U = 2.0 ** -24      # half an fp32 ulp, relative
 AGEM_CASE = dict(STEP_CASES["er_c10"], agent="AGEM", seed=14, tasks=[[0, 1], [2, 3], [4, 5]], n_train=30, n_test=20, mem_size=50,
                  eps_mem_batch=10)
 GOLDEN_KEYS = ("acc", "buf_label", "buf_rowsum", "counters", "state")
+# the nested loops of agents/agem.py:32-38: two epochs of three batches, two memory iterations per batch (each with a draw from the
+# memory and a projection of its own from the second task on), ONE reservoir update after them; recorded as `agem_loops`
+AGEM_LOOPS_CASE = dict(AGEM_CASE, seed=15, tasks=[[0, 1], [2, 3]], n_train=15, epoch=2, mem_iters=2)
+LOOPS_KEYS = GOLDEN_KEYS + ("nbt",)          # + num_batches_tracked of every BatchNorm: the count of train-mode forwards
 
 
 # ---- the projection in float64 ---------------------------------------------------------------------------------------------------------
@@ -64,8 +68,8 @@ def with_cosine(rng, r, cos):
 
 # ---- one iteration of the reference agent ------------------------------------------------------------------------------------------------
 
-def agem_step(state, names, buf, bx, by, eps, lr, task_seen, kd=None):
-    """agents/agem.py:38-83 for ONE stream batch (mem_iters 1): batch pass; from the second task on a uniform draw from the memory,
+def agem_step(state, names, buf, bx, by, eps, lr, task_seen, kd=None, update=True):
+    """agents/agem.py:38-83 for ONE stream batch (mem_iters 1; update=False: one pass of the mem_iters loop, :39-81, slots None): batch pass; from the second task on a uniform draw from the memory,
     the memory pass and the reference's own fp32 projection statements (per-tensor torch.sum, the builtin sum, g - prod / prod_ref * g_r);
     SGD step; reservoir update.  kd(loss, logits, x) -> loss: the KD tricks' blend (:41-46)."""
     net = O.OracleNet(state, head=None, training=True)
@@ -99,7 +103,7 @@ def agem_step(state, names, buf, bx, by, eps, lr, task_seen, kd=None):
             info["loss_mem"] = float(loss_mem.detach())
             info["cos"] = float((g64 @ r64) / (g64.norm() * r64.norm()))
     O.sgd_step(state, names, lr)
-    info["slots"] = O.reservoir_update(buf, bx, by)
+    info["slots"] = O.reservoir_update(buf, bx, by) if update else None
     return info
 
 
@@ -112,18 +116,25 @@ class AgemOracle(O.OracleAgent):
         ys = torch.from_numpy(np.asarray(y)).long()
         loader = torch.utils.data.DataLoader(O._Idx(len(ys)), batch_size=self.batch, shuffle=True, drop_last=True)
         kd = self._kd_mix if (self.trick.get("kd_trick") or self.trick.get("kd_trick_star")) else None
-        for idx in loader:
-            self.log.append(agem_step(self.state, self.names, self.buf, xs[idx], ys[idx], self.p["eps_mem_batch"], self.p["lr"],
-                                      self.task_seen, kd=kd))
+        for ep in range(self.epoch):                     # agem.py:32: a fresh permutation per epoch
+            for idx in loader:
+                parts = [agem_step(self.state, self.names, self.buf, xs[idx], ys[idx], self.p["eps_mem_batch"], self.p["lr"],
+                                   self.task_seen, kd=kd, update=False) for j in range(self.mem_iters)]      # :38
+                slots = O.reservoir_update(self.buf, xs[idx], ys[idx])                                       # :83, once per batch
+                if self.mem_iters == 1:
+                    self.log.append(dict(parts[0], slots=slots))
+                else:                                    # per-j lists
+                    self.log.append(dict({k: [p[k] for p in parts] for k in parts[0] if k != "slots"}, slots=slots))
         self.after_train(new)
 
 
 def record(acc, buf_label, buf_img, current_index, n_seen_so_far, state_dict):
     """What the golden file keeps per task (the arrays of oracle/make_golden.py's step cases)."""
-    from oracle.synth import digest_state
+    from oracle.synth import digest_state, digest_nbt
     return dict(acc=np.asarray(acc, dtype=np.float64), buf_label=np.asarray(buf_label).copy(),
                 buf_rowsum=buf_img.double().sum(dim=(1, 2, 3)).cpu().numpy(),
-                counters=np.array([current_index, n_seen_so_far], dtype=np.int64), state=digest_state(state_dict))
+                counters=np.array([current_index, n_seen_so_far], dtype=np.int64), state=digest_state(state_dict),
+                nbt=digest_nbt(state_dict))
 
 
 def run_oracle_case(cfg=None):

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from oracle import ocl_oracle as O
-from oracle.synth import STEP_CASES, make_stream, seed_all, case_params, digest_state
+from oracle.synth import STEP_CASES, make_stream, seed_all, case_params, digest_state, digest_nbt
 
 U = 2.0 ** -24      # half an fp32 ulp, relative
 TINY = 2.0 ** -149  # the smallest fp32 denormal: what a result that underflows can be off by
@@ -20,6 +20,11 @@ EWC_CASE = dict(STEP_CASES["er_c10"], agent="EWC", seed=14, tasks=[[0, 1], [2, 3
 EWC_KEYS = ("lambda_", "alpha", "fisher_update_after", "learning_rate")
 FISHER_KEYS = ("running", "tmp", "normalized", "prev")
 GOLDEN_KEYS = ("acc", "state", "minmax") + FISHER_KEYS
+# two epochs of three batches with the running Fisher updated after every second iteration, counted ACROSS the epochs
+# (ewc_pp.py:41: (ep * len(train_loader) + i + 1) % fisher_update_after): iterations 1 | 3 and 5 of a task, i.e. i = 1 in the first epoch
+# and i = 0, 2 in the second; recorded as `ewc_loops`
+EWC_LOOPS_CASE = dict(EWC_CASE, seed=15, tasks=[[0, 1], [2, 3]], n_train=15, epoch=2)
+LOOPS_KEYS = GOLDEN_KEYS + ("nbt", "ema_at")      # + num_batches_tracked per BatchNorm, + the task's iterations (0-based) that began with the update
 
 
 def ref_params(cfg):
@@ -159,6 +164,7 @@ class EwcOracle(O.OracleAgent):
         self.ewc = SimpleNamespace(prev=OrderedDict(), running=init_fisher(self.state, self.names), tmp=init_fisher(self.state, self.names),
                                    normalized=init_fisher(self.state, self.names))
         self.minmax = []
+        self.ema_at = []            # per train_learner call: the iterations (0-based, counted over the epochs) that began with the moving average
 
     def update_running_fisher(self):
         e = self.ewc
@@ -173,11 +179,14 @@ class EwcOracle(O.OracleAgent):
         loader = torch.utils.data.DataLoader(O._Idx(len(ys)), batch_size=self.batch, shuffle=True, drop_last=True)
         kd = self._kd_mix if (self.trick.get("kd_trick") or self.trick.get("kd_trick_star")) else None
         e = self.ewc
-        for i, idx in enumerate(loader):
-            ema = (i + 1) % self.fisher_update_after == 0          # one epoch: ep * len(loader) + i + 1
-            if ema:
-                self.update_running_fisher()
-            self.log.append(dict(ewc_step(self.state, self.names, e, xs[idx], ys[idx], self.p["lr"], self.lambda_, kd=kd), ema=ema))
+        self.ema_at.append([])
+        for ep in range(self.epoch):                               # ewc_pp.py:33: a fresh permutation per epoch
+            for i, idx in enumerate(loader):
+                ema = (ep * len(loader) + i + 1) % self.fisher_update_after == 0          # :41
+                if ema:
+                    self.update_running_fisher()
+                    self.ema_at[-1].append(ep * len(loader) + i)
+                self.log.append(dict(ewc_step(self.state, self.names, e, xs[idx], ys[idx], self.p["lr"], self.lambda_, kd=kd), ema=ema))
         for n in self.names:
             e.prev[n] = self.state[n].clone().detach()
         max_fisher = max([torch.max(m) for m in e.running.values()])
@@ -193,10 +202,11 @@ class EwcOracle(O.OracleAgent):
         return None if len(d) == 0 else torch.cat([d[n].detach().reshape(-1) for n in self.names])
 
 
-def record(acc, state_dict, running, tmp, normalized, prev):
+def record(acc, state_dict, running, tmp, normalized, prev, ema_at=()):
     """What the golden file keeps per task: the accuracies, the digest_state rows of the model and of the four dictionaries, and the
-    running Fisher's [min, max]."""
-    return dict(acc=np.asarray(acc, dtype=np.float64), state=digest_state(state_dict),
+    running Fisher's [min, max]; for ewc_loops also num_batches_tracked and the iterations that began with the moving average."""
+    return dict(acc=np.asarray(acc, dtype=np.float64), state=digest_state(state_dict), nbt=digest_nbt(state_dict),
+                ema_at=np.asarray(list(ema_at), dtype=np.int64),
                 minmax=np.array([min(float(v.min()) for v in running.values()), max(float(v.max()) for v in running.values())]),
                 running=digest_state(running), tmp=digest_state(tmp), normalized=digest_state(normalized), prev=digest_state(prev))
 
@@ -212,7 +222,7 @@ def run_oracle_case(cfg=None, tasks_only=None):
     for x, y in tasks[:tasks_only]:
         ag.train_learner(x, y)
         acc = ag.evaluate(tests)
-        recs.append(record(acc, ag.state_dict(), ag.ewc.running, ag.ewc.tmp, ag.ewc.normalized, ag.ewc.prev))
+        recs.append(record(acc, ag.state_dict(), ag.ewc.running, ag.ewc.tmp, ag.ewc.normalized, ag.ewc.prev, ema_at=ag.ema_at[-1]))
     return recs, ag
 
 

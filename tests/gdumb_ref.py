@@ -137,8 +137,8 @@ class GdumbOracle(O.OracleAgent):
 
 
 def gdumb_params(cfg):
-    """What oracle.synth.case_params does not forward."""
-    return dict(batch=cfg["batch"], mem_epoch=cfg["mem_epoch"], clip=cfg["clip"], minlr=0.0005)
+    """What oracle.synth.case_params does not forward (`batch` it does)."""
+    return dict(mem_epoch=cfg["mem_epoch"], clip=cfg["clip"], minlr=0.0005)
 
 
 def record(acc, mem_label, mem_img, mem_c, state_dict):

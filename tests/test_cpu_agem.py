@@ -14,7 +14,7 @@ from oracle import ref_import
 from oracle.synth import make_stream, seed_all, case_params
 from test_cpu_adam import make_grads
 import agem_ref
-from agem_ref import ref_project, project_bound, worst_ratio, with_cosine, AGEM_CASE, GOLDEN_KEYS
+from agem_ref import ref_project, project_bound, worst_ratio, with_cosine, AGEM_CASE, AGEM_LOOPS_CASE, GOLDEN_KEYS
 
 OCL_ERR_ARG = -1    # include/ocl_hip.h
 
@@ -170,6 +170,23 @@ def test_agem_step_free_run_reproduces_the_recorded_reference_run():
     seen = [e for e in ag.log if e["cos"] is not None]
     assert len(ag.log) == 18 and len(seen) == 12 and sum(e["projected"] for e in seen) == 4
     assert all(e["projected"] == (e["cos"] < 0) for e in seen)
+
+
+def test_agem_step_nested_loops_reproduce_the_recorded_reference_run():
+    """agem_loops (epoch 2, mem_iters 2; agents/agem.py:32-38): everything the host RNGs drive and the count of train-mode forwards
+    per BatchNorm are exact against the reference's recording; one log entry per stream batch with per-j lists."""
+    g = gold("agem")
+    recs, ag = agem_ref.run_oracle_case(AGEM_LOOPS_CASE)
+    assert len(recs) == int(g["agem_loops_ntasks"]) == 2
+    for t, rec in enumerate(recs):
+        for k in ("buf_label", "buf_rowsum", "counters", "nbt"):
+            assert np.array_equal(rec[k], g["agem_loops_t%d_%s" % (t, k)]), (t, k)
+    # 2 epochs x 3 batches x 2 passes: one forward each in the first task (12), two each in the second (24)
+    assert g["agem_loops_t0_nbt"].tolist() == [12] * 20 and g["agem_loops_t1_nbt"].tolist() == [36] * 20
+    assert g["agem_loops_t1_counters"].tolist() == [50, 120]
+    assert len(ag.log) == 12 and all(len(e["loss"]) == 2 and len(e["idx"]) == 2 for e in ag.log)
+    assert all(e["cos"] == [None, None] for e in ag.log[:6]) and all(None not in e["cos"] for e in ag.log[6:])
+    assert all(p == (c < 0) for e in ag.log[6:] for p, c in zip(e["projected"], e["cos"]))
 
 
 @pytest.mark.parametrize("seed", [14, 15, 16])

@@ -18,7 +18,7 @@ from oracle import ref_import
 from oracle.synth import make_stream, seed_all
 from test_cpu_adam import make_grads
 import ewc_ref
-from ewc_ref import EWC_CASE, GOLDEN_KEYS, FISHER_KEYS
+from ewc_ref import EWC_CASE, EWC_LOOPS_CASE, GOLDEN_KEYS, FISHER_KEYS
 
 OCL_ERR_ARG = -1    # include/ocl_hip.h
 HIPCC = "/opt/rocm/bin/hipcc"
@@ -353,3 +353,17 @@ def test_ewc_kernels_use_no_scratch():
     assert len(scratch) == 9, sorted(scratch)
     bad = {k: v for k, v in scratch.items() if v}
     assert not bad, "scratch in an EWC++ kernel: %s" % bad
+
+
+def test_ewc_oracle_two_epochs_reproduce_the_recorded_schedule_and_forward_counts():
+    """ewc_loops (epoch 2, three batches per epoch, fisher_update_after 2): the reference's counter runs across the epochs
+    (ewc_pp.py:41), so the running Fisher is updated at the task's iterations 1, 3, 5 -- i = 1 in the first epoch, i = 0 and 2 in the
+    second -- and not at i = 1 twice.  The sequence and num_batches_tracked are exact against the reference's recording."""
+    g = gold("ewc")
+    recs, ag = ewc_ref.run_oracle_case(EWC_LOOPS_CASE)
+    assert len(recs) == int(g["ewc_loops_ntasks"]) == 2
+    for t, rec in enumerate(recs):
+        assert np.array_equal(rec["ema_at"], g["ewc_loops_t%d_ema_at" % t]) and rec["ema_at"].tolist() == [1, 3, 5]
+        assert np.array_equal(rec["nbt"], g["ewc_loops_t%d_nbt" % t]) and rec["nbt"].tolist() == [6 * (t + 1)] * 20
+    assert [e["ema"] for e in ag.log] == [False, True, False, True, False, True] * 2
+    assert "ewc_c10_t0_ema_at" not in g.files and "ewc_c10_t0_nbt" not in g.files

@@ -6,7 +6,7 @@ import torch
 
 from conftest import gold
 from oracle import ocl_oracle as O
-from oracle.synth import STEP_CASES, make_stream, seed_all, digest_state
+from oracle.synth import STEP_CASES, make_stream, seed_all, digest_state, digest_nbt, digest_rng, case_params
 
 
 def test_knn_sv_matches_reference_bit_exact():
@@ -149,7 +149,8 @@ def test_resnet_forward_backward_matches_reference(name, agent, data, hw, n, hea
 @pytest.mark.parametrize("name", [n for n, c in STEP_CASES.items() if c.get("golden", True)])
 def test_step_cases_match_reference_runs(name):
     """Whole tasks (train_learner + evaluate) of the oracle agent vs the reference agent's recorded run: buffer labels,
-    counters and accuracies exact; weights / BN buffers / buffer images within 1e-6 relative (same ATen kernels)."""
+    counters and accuracies exact; weights / BN buffers / buffer images within 1e-6 relative (same ATen kernels); the count of
+    train-mode forwards per BatchNorm (num_batches_tracked) and the position of the host generators after evaluate() exact."""
     g = gold("steps")
     cfg = STEP_CASES[name]
     torch.set_num_threads(1)
@@ -163,6 +164,43 @@ def test_step_cases_match_reference_runs(name):
         assert np.array_equal(ag.buf.label.numpy(), g[pre + "buf_label"])
         assert [ag.buf.current_index, ag.buf.n_seen_so_far] == g[pre + "counters"].tolist()
         assert np.array_equal(acc, g[pre + "acc"])
+        assert np.array_equal(digest_nbt(ag.state_dict()), g[pre + "nbt"]) and g[pre + "nbt"].dtype == np.int64
+        assert np.array_equal(digest_rng(), g[pre + "rng"]) and g[pre + "rng"].dtype == np.int64
         assert np.abs(ag.buf.img.double().sum(dim=(1, 2, 3)).numpy() - g[pre + "buf_rowsum"]).max() < 1e-6
         ds, gs = digest_state(ag.state_dict()), g[pre + "state"]
         assert np.abs(ds - gs).max() <= 1e-6 * (1 + np.abs(gs).max())
+
+
+def test_case_params_forwards_the_loop_keys_only_when_a_case_names_them():
+    """epoch, mem_iters, batch, weight_decay and learning_rate reach the agents' parameters from the cases that name them; a case that
+    names none gives the dictionary it always gave."""
+    loop_keys = {"epoch", "mem_iters", "batch", "weight_decay", "learning_rate"}
+    assert not loop_keys & set(case_params(STEP_CASES["er_c10"]))
+    assert set(case_params(STEP_CASES["er_c10"])) == {"agent", "retrieve", "update", "data", "mem_size", "eps_mem_batch", "seed", "num_tasks"}
+    p = case_params(STEP_CASES["er_uneven"])
+    assert {k: p[k] for k in loop_keys} == dict(epoch=1, mem_iters=2, batch=8, weight_decay=1e-4, learning_rate=0.05)
+    p = case_params(STEP_CASES["scr_loops"])
+    assert (p["epoch"], p["mem_iters"]) == (2, 2) and not {"batch", "weight_decay", "learning_rate"} & set(p)
+
+
+def test_oracle_agent_nests_epochs_and_memory_iterations():
+    """The oracle agent's loop shape on er_uneven's first task (60 samples at batch 8: 7 batches, 4 dropped): one log entry per stream
+    batch with per-j lists, ONE reservoir update per entry, 2 * 7 batch passes + 2 * 6 memory passes; and the one-iteration step
+    functions still return what they returned (`slots` / `upd` present, scalars not lists)."""
+    cfg = STEP_CASES["er_uneven"]
+    torch.set_num_threads(1)
+    seed_all(cfg["seed"])
+    ag = O.OracleAgent(cfg)
+    tasks, _ = make_stream(cfg)
+    ag.train_learner(*tasks[0])
+    assert len(ag.log) == 7 and ag.buf.n_seen_so_far == 56
+    assert all(len(e["loss"]) == 2 and len(e["idx"]) == 2 and isinstance(e["slots"], list) for e in ag.log)
+    assert [len(i) for i in ag.log[0]["idx"]] == [0, 0] and [len(i) for i in ag.log[1]["idx"]] == [8, 8]
+    assert all([len(i) for i in e["idx"]] == [12, 12] for e in ag.log[2:])
+    assert set(digest_nbt(ag.state_dict()).tolist()) == {2 * 7 + 2 * 6}
+    buf = O.OracleBuffer(20, (3, 32, 32))
+    x, y = O.to_tensor(tasks[0][0][:8]), torch.from_numpy(tasks[0][1][:8])
+    info = O.er_step(ag.state, ag.names, buf, x, y, ag.p)
+    assert isinstance(info["loss"], float) and info["slots"] == list(range(8)) and len(info["idx"]) == 0
+    info = O.er_step(ag.state, ag.names, buf, x, y, ag.p, update=False)
+    assert "slots" not in info and len(info["idx"]) == 8 and buf.n_seen_so_far == 8

@@ -12,10 +12,10 @@ import pytest
 import torch
 
 from conftest import gold
-from oracle.synth import make_stream, seed_all, digest_state, case_params, class_images
+from oracle.synth import make_stream, seed_all, digest_state, digest_nbt, case_params, class_images
 from test_cpu_adam import make_grads
 import agem_ref
-from agem_ref import ref_project, worst_ratio, with_cosine, AGEM_CASE
+from agem_ref import ref_project, worst_ratio, with_cosine, AGEM_CASE, AGEM_LOOPS_CASE
 
 pytestmark = pytest.mark.gpu
 
@@ -358,6 +358,50 @@ def test_cosim_agem(cuda):
     assert len(kinds[True]) >= 3 and len(kinds[False]) >= 3
 
 
+def test_cosim_agem_inner_steps(cuda):
+    """agem_loops' stream, one stream batch per call at mem_iters 2 (agents/agem.py:38): two batch passes, from the second call on two
+    draws from the memory and two projections, then ONE reservoir update.  Host RNG state, both retrievals, the slots and the buffers
+    exact; the first pass starts from identical state: its two losses within 1e-4 and its decision the oracle's (|cos| is printed; the
+    CPU test of the case shows it is never close to zero in the free run)."""
+    from ocl_amd import debug
+    cfg = dict(AGEM_LOOPS_CASE, epoch=1)
+    params, model, opt, agent = _build_agent(cfg)
+    assert agent.mem_iters == 2
+    seed_all(cfg["seed"])
+    oa = agem_ref.AgemOracle(cfg)
+    xs, ys = agem_ref.cosim_stream(cfg)
+    seed_all(1000 + cfg["seed"])
+    for it in range(6):
+        x, y = xs[it * 10:(it + 1) * 10], ys[it * 10:(it + 1) * 10]
+        model.load_state_dict(oa.state_dict())
+        st = _rng_get()
+        oa.train_learner(x, y)
+        ol = oa.log[-1]
+        st_o = _rng_get()
+        _rng_set(st)
+        debug.LOG = []
+        try:
+            agent.train_learner(x, y)
+            ev = list(debug.LOG)
+        finally:
+            debug.LOG = None
+        assert _rng_equal(st_o, _rng_get()), "host RNG streams diverged at call %d" % it
+        loss = _events(ev, "agem_loss")
+        assert len(loss) == 2 and abs(loss[0]["loss"] - ol["loss"][0]) < 1e-4, (loss, ol["loss"])
+        rr, proj, loss_mem = _events(ev, "random_retrieve"), _events(ev, "agem"), _events(ev, "agem_loss_mem")
+        if it == 0:
+            assert not rr and not proj and not loss_mem and ol["cos"] == [None, None]
+        else:
+            assert len(rr) == 2 and all(np.array_equal(a["indices"], b) for a, b in zip(rr, ol["idx"])), "retrieval of pass j differs"
+            assert len(loss_mem) == 2 and abs(loss_mem[0]["loss"] - ol["loss_mem"][0]) < 1e-4, (loss_mem, ol["loss_mem"])
+            assert len(proj) == 2
+            print("agem_loops call %d  cos %s  projected %s (oracle %s)" % (it, ["%+.4f" % c for c in ol["cos"]], [p["projected"] for p in proj], ol["projected"]))
+            if abs(ol["cos"][0]) >= 1e-3:
+                assert proj[0]["projected"] == ol["projected"][0], (it, proj[0], ol["cos"])
+        assert [list(e["slots"]) for e in _events(ev, "reservoir")] == [list(ol["slots"])], "one reservoir update per stream batch"
+        assert _buffers_equal(agent, oa)
+
+
 # ---- 5. the comparator ------------------------------------------------------------------------------------------------------------------
 
 COMPARATOR_BOUND = 1e-4
@@ -441,6 +485,34 @@ def test_free_run_vs_reference_golden(cuda):
         rel = np.abs(ds - gs).max() / (1e-12 + np.abs(gs).max())
         ratio = np.sqrt((ds[:, 1] ** 2).sum() / (gs[:, 1] ** 2).sum())
         print("agem_c10", t, "state digest rel err", rel, "norm ratio", ratio, "acc", acc, g[pre + "acc"])
+        assert np.isfinite(ds).all() and 0.5 < ratio < 2.0 and rel < 3.0, (rel, ratio)
+        assert acc.shape == g[pre + "acc"].shape and (acc >= 0).all() and (acc <= 1).all()
+
+
+def test_free_run_nested_loops_vs_reference_golden(cuda):
+    """agem_loops (epoch 2, mem_iters 2), free running, against the reference's recording: the replay memory, the counters and the count
+    of train-mode forwards per BatchNorm (one per pass in the first task, two from the second on) exact; the weights get the sanity band."""
+    from ocl_amd.data import setup_test_loader
+    g = gold("agem")
+    cfg = AGEM_LOOPS_CASE
+    params, model, opt, agent = _build_agent(cfg)
+    assert (agent.epoch, agent.mem_iters) == (2, 2)
+    tasks, tests = make_stream(cfg)
+    loaders = setup_test_loader(tests, params)
+    for t, (x, y) in enumerate(tasks):
+        agent.train_learner(x, y)
+        acc = agent.evaluate(loaders)
+        pre = "agem_loops_t%d_" % t
+        assert np.array_equal(agent.buffer.buffer_label.cpu().numpy(), g[pre + "buf_label"]), "buffer labels differ from the reference"
+        assert np.array_equal(agent.buffer.label_host, g[pre + "buf_label"]), "host label mirror out of step"
+        assert [agent.buffer.current_index, agent.buffer.n_seen_so_far] == g[pre + "counters"].tolist()
+        rs = agent.buffer.buffer_img.double().sum(dim=(1, 2, 3)).cpu().numpy()
+        assert np.abs(rs - g[pre + "buf_rowsum"]).max() < 1e-6, "buffer images differ (slot indices or image bytes)"
+        assert digest_nbt(model.state_dict()).tolist() == g[pre + "nbt"].tolist(), "train-mode forward count differs from the reference"
+        ds, gs = digest_state(model.state_dict()), g[pre + "state"]
+        rel = np.abs(ds - gs).max() / (1e-12 + np.abs(gs).max())
+        ratio = np.sqrt((ds[:, 1] ** 2).sum() / (gs[:, 1] ** 2).sum())
+        print("agem_loops", t, "state digest rel err", rel, "norm ratio", ratio, "acc", acc, g[pre + "acc"])
         assert np.isfinite(ds).all() and 0.5 < ratio < 2.0 and rel < 3.0, (rel, ratio)
         assert acc.shape == g[pre + "acc"].shape and (acc >= 0).all() and (acc <= 1).all()
 

@@ -13,10 +13,10 @@ import pytest
 import torch
 
 from conftest import gold
-from oracle.synth import make_stream, seed_all, digest_state
+from oracle.synth import make_stream, seed_all, digest_state, digest_nbt
 from test_cpu_adam import make_grads
 import ewc_ref
-from ewc_ref import EWC_CASE, ema_f32, normalize_f32
+from ewc_ref import EWC_CASE, EWC_LOOPS_CASE, ema_f32, normalize_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -637,6 +637,46 @@ def test_free_run_vs_reference_golden(cuda):
         assert float(nf.min()) == 0.0 and float(nf.max()) == 1.0 and torch.equal(_bits(agent.prev_params), _bits(model.flat_params()))
         pn, gn = float(agent.prev_params.double().norm()), np.sqrt((g[pre + "prev"][:, 1] ** 2).sum())
         assert 0.5 < pn / gn < 2.0, (pn, gn)
+
+
+def test_free_run_two_epochs_schedule_and_forward_counts_vs_reference_golden(cuda):
+    """ewc_loops (epoch 2, three batches per epoch, fisher_update_after 2), free running with the trace on, against the reference's
+    recording: the task's iterations that begin with the running Fisher's moving average (1, 3, 5: the counter of ewc_pp.py:41 runs
+    across the epochs, so the second epoch updates at other i than the first) and num_batches_tracked exact; the very first step
+    starts from the seeded initial weights on both sides, its cross-entropy within 1e-4 (the co-simulation's bound); the weights get
+    the sanity band of the free run above."""
+    from ocl_amd import debug
+    from ocl_amd.data import setup_test_loader
+    g = gold("ewc")
+    cfg = EWC_LOOPS_CASE
+    params, model, opt, agent = _build_agent(cfg)
+    assert agent.epoch == 2 and agent.fisher_update_after == 2
+    tasks, tests = make_stream(cfg)
+    loaders = setup_test_loader(tests, params)
+    for t, (x, y) in enumerate(tasks):
+        debug.LOG = []
+        try:
+            agent.train_learner(x, y)
+            ev = list(debug.LOG)
+        finally:
+            debug.LOG = None
+        acc = agent.evaluate(loaders)
+        pre = "ewc_loops_t%d_" % t
+        tags = [tag for tag, _ in ev if tag in ("ewc_loss", "ewc_fisher_update")]
+        ema_at = [tags[:k].count("ewc_loss") for k, tag in enumerate(tags) if tag == "ewc_fisher_update"]
+        assert tags.count("ewc_loss") == 6 and ema_at == g[pre + "ema_at"].tolist() == [1, 3, 5], (tags, g[pre + "ema_at"])
+        assert digest_nbt(model.state_dict()).tolist() == g[pre + "nbt"].tolist(), "train-mode forward count differs from the reference"
+        if t == 0:
+            first = _events(ev, "ewc_loss")[0]
+            assert abs(first["loss"] - g["ewc_loops_ce"][0]) < 1e-4 and first["penalty"] == 0.0, (first, g["ewc_loops_ce"][0])
+        ds, gs = digest_state(model.state_dict()), g[pre + "state"]
+        rel = np.abs(ds - gs).max() / (1e-12 + np.abs(gs).max())
+        ratio = np.sqrt((ds[:, 1] ** 2).sum() / (gs[:, 1] ** 2).sum())
+        hi, ghi = float(agent.running_fisher.max()), g[pre + "minmax"][1]
+        print("ewc_loops", t, "updates at", ema_at, "state digest rel err", rel, "norm ratio", ratio, "running Fisher max", hi, "recorded", ghi, "acc", acc)
+        assert np.isfinite(ds).all() and 0.5 < ratio < 2.0 and rel < 3.0, (rel, ratio)
+        assert 0.5 < hi / ghi < 2.0, (hi, ghi)
+        assert acc.shape == g[pre + "acc"].shape and (acc >= 0).all() and (acc <= 1).all()
 
 
 # ---- 10. with Adam ----------------------------------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ import torch
 
 from conftest import gold
 from oracle import ocl_oracle as O
-from oracle.synth import STEP_CASES, make_stream, seed_all, digest_state, case_params, class_images
+from oracle.synth import STEP_CASES, make_stream, seed_all, digest_state, digest_nbt, digest_rng, case_params, class_images
 
 pytestmark = pytest.mark.gpu
 
@@ -66,6 +66,10 @@ def test_free_running_cases_vs_reference_golden(cuda, name):
         assert np.array_equal(agent.buffer.buffer_label.cpu().numpy(), g[pre + "buf_label"]), "buffer labels differ from the reference"
         assert np.array_equal(agent.buffer.label_host, g[pre + "buf_label"]), "host label mirror out of step"
         assert [agent.buffer.current_index, agent.buffer.n_seen_so_far] == g[pre + "counters"].tolist()
+        # integer invariants of the loop: the count of train-mode forwards per BatchNorm, and where the host generators stand after
+        # evaluate() (every permutation, retrieval and reservoir draw of the task taken, none twice)
+        assert digest_nbt(model.state_dict()).tolist() == g[pre + "nbt"].tolist(), "train-mode forward count differs from the reference"
+        assert digest_rng().tolist() == g[pre + "rng"].tolist(), "host RNG streams are not where the reference leaves them"
         rs = agent.buffer.buffer_img.double().sum(dim=(1, 2, 3)).cpu().numpy()
         assert np.abs(rs - g[pre + "buf_rowsum"]).max() < 1e-6, "buffer images differ (slot indices or image bytes)"
         ds, gs = digest_state(model.state_dict()), g[pre + "state"]
@@ -100,10 +104,28 @@ def _flat(state, names):
     return torch.cat([state[k].detach().reshape(-1) for k in names]).double().numpy()
 
 
-def cosim(cfg, n_iters, cuda, prefill=None, x_stream=None, before_hip=None, sync_extra=None):
+def _oracle_self_distance(oa, x, y, st, w0, dw_o):
+    """The oracle's own sensitivity for one call: the same call from a copy of the oracle whose weights are moved by one unit in the
+    last place (up / down; test_gpu_parity2._oracle_run's perturbation), same memory, same host RNG state.  -> the larger norm-wise
+    difference of the two updates from the unperturbed oracle's, relative to the latter."""
+    out = 0.0
+    for ulp in (1, -1):
+        ob = copy.deepcopy(oa)
+        with torch.no_grad():
+            for k in ob.names:
+                ob.state[k].copy_(torch.nextafter(ob.state[k].detach(), torch.full_like(ob.state[k], float("inf") * ulp)))
+        wp0 = _flat(ob.state, ob.names)
+        _rng_set(st)
+        ob.train_learner(x, y)
+        out = max(out, float(np.linalg.norm((_flat(ob.state, ob.names) - wp0) - dw_o) / (1e-30 + np.linalg.norm(dw_o))))
+    return out
+
+
+def cosim(cfg, n_iters, cuda, prefill=None, x_stream=None, before_hip=None, sync_extra=None, batch=10, self_distance=False):
     """Yields per iteration (events of the HIP agent, oracle log entry, dict of checks already made).  Before every
     iteration the HIP model is loaded with the oracle's weights and BatchNorm buffers (teacher forcing); both sides then
-    consume the SAME host RNG streams (state saved / restored), and must leave them in the same state."""
+    consume the SAME host RNG streams (state saved / restored), and must leave them in the same state.  `batch` samples are fed per
+    call; self_distance=True adds the oracle's own +-1-ulp sensitivity for the same call (`self_dist`)."""
     from ocl_amd import debug
     params, model, agent = build_agent(cfg)
     seed_all(cfg["seed"])
@@ -114,10 +136,10 @@ def cosim(cfg, n_iters, cuda, prefill=None, x_stream=None, before_hip=None, sync
         tasks, _ = make_stream(cfg)
         x_stream = tasks[0]
     xs, ys = x_stream
-    assert len(ys) >= n_iters * 10
+    assert len(ys) >= n_iters * batch
     seed_all(1000 + cfg["seed"])
     for it in range(n_iters):
-        x, y = xs[it * 10:(it + 1) * 10], ys[it * 10:(it + 1) * 10]
+        x, y = xs[it * batch:(it + 1) * batch], ys[it * batch:(it + 1) * batch]
         model.load_state_dict(oa.state_dict())
         if sync_extra is not None:
             sync_extra(agent, oa)          # plugin state beyond weights / memory (e.g. GSS slot scores)
@@ -126,8 +148,10 @@ def cosim(cfg, n_iters, cuda, prefill=None, x_stream=None, before_hip=None, sync
         w0 = _flat(oa.state, oa.names)
         st = _rng_get()
         n_log = len(oa.log)
+        probe = copy.deepcopy(oa) if self_distance else None
         oa.train_learner(x, y)
         st_o = _rng_get()
+        self_dist = _oracle_self_distance(probe, x, y, st, w0, _flat(oa.state, oa.names) - w0) if self_distance else None
         _rng_set(st)
         if before_hip is not None:
             before_hip(oa.log[-1])
@@ -144,7 +168,7 @@ def cosim(cfg, n_iters, cuda, prefill=None, x_stream=None, before_hip=None, sync
         dw_o, dw_m = w1_o - w0, w1_m - w0
         upd_err = float(np.linalg.norm(dw_m - dw_o) / (1e-30 + np.linalg.norm(dw_o))) if np.linalg.norm(dw_o) > 0 else float(np.linalg.norm(dw_m))
         yield it, ev, oa.log[-1], dict(rng_equal=_rng_equal(st_o, st_m), upd_err=upd_err, agent=agent, oa=oa, model=model,
-                                       state_before=state_before, buf_before=buf_before)
+                                       state_before=state_before, buf_before=buf_before, self_dist=self_dist, w0=w0, dw_err=dw_m - dw_o)
 
 
 def _buffers_equal(agent, oa):
@@ -447,54 +471,88 @@ def test_reference_style_agent_code_runs_on_the_engine(cuda):
     assert torch.allclose(model.flat_params(), before - 0.1 * g, atol=1e-7)
 
 
+def _bn_state(model):
+    """BatchNorm running statistics and num_batches_tracked (the exact count of train-mode forwards, per layer)."""
+    return {k: v.cpu().numpy().copy() for k, v in model.state_dict().items() if "running" in k or "num_batches" in k}
+
+
+def _assert_bn_state(r1, r0, rel=None):
+    """num_batches_tracked exact always; the running statistics exact (rel None) or within `rel` of the tensor's largest element."""
+    assert any("num_batches" in k for k in r0)
+    for k in r0:
+        if rel is None or "num_batches" in k:
+            assert np.array_equal(r1[k], r0[k]), k
+        else:
+            assert np.abs(r1[k] - r0[k]).max() < rel * max(1.0, np.abs(r0[k]).max()), k
+
+
+# The five schedule-only comparisons below take the loop shape as arguments: the tests of this file run them at epoch 1 / mem_iters 1,
+# tests/test_gpu_loops.py at epoch 2 / mem_iters 2 on a third of the samples (as many steps).  n_seen counts every epoch's samples.
+
 def test_scr_data_stream_overlap_is_schedule_only(cuda, monkeypatch):
     """agents/scr.py issues the data path (loader gather, random retrieve, concat, augmentation, reservoir scatter) on its own
     stream so that it runs next to the previous step's backward.  Same statements, same RNG draws: 60 free-running SCR steps
     (real augmentation kernel, buffer filling up and being overwritten) with and without the overlap must end in the same
     replay buffer bit for bit and the same weights up to the order of the fp64 statistic atomics."""
-    cfg = dict(STEP_CASES["scr_c100"], mem_size=200)
+    scr_data_stream_overlap_legs(cuda, monkeypatch, 1, 1, 600)
+
+
+def scr_data_stream_overlap_legs(cuda, monkeypatch, epoch, mem_iters, n):
+    cfg = dict(STEP_CASES["scr_c100"], mem_size=200, epoch=epoch, mem_iters=mem_iters)
     rng = np.random.default_rng(77)
-    x = rng.integers(0, 256, (600, 32, 32, 3), dtype=np.uint8)
-    y = rng.integers(0, 10, 600).astype(np.int64)
+    x = rng.integers(0, 256, (n, 32, 32, 3), dtype=np.uint8)
+    y = rng.integers(0, 10, n).astype(np.int64)
     finals = []
     for flag in ("1", "0"):
         monkeypatch.setenv("OCL_DATA_STREAM", flag)
         params, model, agent = build_agent(cfg)
+        assert (agent.epoch, agent.mem_iters) == (epoch, mem_iters)
         from ocl_amd.agents.scr import ScrAugment
         agent.transform = ScrAugment(size=(32, 32), scale=(0.2, 1.))
         agent.train_learner(torch.from_numpy(x).to(cuda), y)
         torch.cuda.synchronize()
         finals.append((model.flat_params().cpu().numpy().copy(), agent.buffer.buffer_img.cpu().numpy().copy(),
-                       agent.buffer.buffer_label.cpu().numpy().copy(), agent.buffer.n_seen_so_far))
-    (w1, b1, l1, n1), (w0, b0, l0, n0) = finals
-    assert n1 == n0 == 600 and np.array_equal(l1, l0) and np.array_equal(b1, b0)
+                       agent.buffer.buffer_label.cpu().numpy().copy(), agent.buffer.n_seen_so_far, _bn_state(model)))
+    (w1, b1, l1, n1, r1), (w0, b0, l0, n0, r0) = finals
+    assert n1 == n0 == epoch * n and np.array_equal(l1, l0) and np.array_equal(b1, b0)
     assert np.abs(w1 - w0).max() < 1e-4 * max(1.0, np.abs(w0).max())
+    _assert_bn_state({k: v for k, v in r1.items() if "num_batches" in k}, {k: v for k, v in r0.items() if "num_batches" in k})
 
 
 def test_er_data_stream_overlap_is_schedule_only(cuda, monkeypatch):
     """agents/exp_replay.py (random retrieve / reservoir update, merged two-group pass) issues its data path on the data stream as
     agents/scr.py does.  Same statements, same RNG draws, and the batch sums are order-independent: 60 free-running ER steps (memory
     filling up and being overwritten) with and without the overlap end in the same replay memory AND the same weights, bit for bit."""
+    er_data_stream_overlap_legs(cuda, monkeypatch, 1, 1, 600)
+
+
+def er_data_stream_overlap_legs(cuda, monkeypatch, epoch, mem_iters, n, **over):
+    """`over`: further keys of the case (tests/test_gpu_loops.py: batch 8 against eps_mem_batch 12, the non-merged pass with a
+    retrieval fetched on the data stream)."""
     from ocl_amd import ops
     ops.set_deterministic(True)   # (bit-identical weights need the order-independent batch sums; restored below)
-    cfg = dict(STEP_CASES["er_c10"], mem_size=200)
+    cfg = dict(STEP_CASES["er_c10"], mem_size=200, epoch=epoch, mem_iters=mem_iters)
+    cfg.update(over)
+    batch = cfg.get("batch", 10)
     rng = np.random.default_rng(79)
-    x = rng.integers(0, 256, (600, 32, 32, 3), dtype=np.uint8)
-    y = rng.integers(0, 10, 600).astype(np.int64)
+    x = rng.integers(0, 256, (n, 32, 32, 3), dtype=np.uint8)
+    y = rng.integers(0, 10, n).astype(np.int64)
     finals = []
     try:
         for flag in ("1", "0"):
             monkeypatch.setenv("OCL_DATA_STREAM", flag)
             params, model, agent = build_agent(cfg)
+            assert (agent.epoch, agent.mem_iters, agent.batch) == (epoch, mem_iters, batch)
             agent.train_learner(torch.from_numpy(x).to(cuda), y)
             torch.cuda.synchronize()
             finals.append((model.flat_params().cpu().numpy().copy(), agent.buffer.buffer_img.cpu().numpy().copy(),
-                           agent.buffer.buffer_label.cpu().numpy().copy(), agent.buffer.n_seen_so_far))
+                           agent.buffer.buffer_label.cpu().numpy().copy(), agent.buffer.n_seen_so_far, _bn_state(model)))
     finally:
         ops.set_deterministic(False)   # (also when a step raised: the rest of the session must not run in the integer-sum mode)
-    (w1, b1, l1, n1), (w0, b0, l0, n0) = finals
-    assert n1 == n0 == 600 and np.array_equal(l1, l0) and np.array_equal(b1, b0)
+    (w1, b1, l1, n1, r1), (w0, b0, l0, n0, r0) = finals
+    assert n1 == n0 == epoch * (n // batch) * batch and np.array_equal(l1, l0) and np.array_equal(b1, b0)
     assert np.array_equal(w1, w0)
+    _assert_bn_state(r1, r0)
 
 
 def test_er_merged_step_direct_backward_is_schedule_only(cuda):
@@ -502,29 +560,32 @@ def test_er_merged_step_direct_backward_is_schedule_only(cuda):
     launches wrote, instead of letting autograd assemble it (two slice-backward fills, two copies, an add, the loss add).  Same numbers
     into the same backward: with order-independent batch sums 60 free-running ER steps end in bit-identical weights, running
     statistics and replay memory on both paths (`_force_autograd` = the autograd path)."""
+    er_merged_step_direct_backward_legs(cuda, 1, 1, 600)
+
+
+def er_merged_step_direct_backward_legs(cuda, epoch, mem_iters, n):
     from ocl_amd import ops
-    cfg = dict(STEP_CASES["er_c10"], mem_size=200)
+    cfg = dict(STEP_CASES["er_c10"], mem_size=200, epoch=epoch, mem_iters=mem_iters)
     rng = np.random.default_rng(81)
-    x = rng.integers(0, 256, (600, 32, 32, 3), dtype=np.uint8)
-    y = rng.integers(0, 10, 600).astype(np.int64)
+    x = rng.integers(0, 256, (n, 32, 32, 3), dtype=np.uint8)
+    y = rng.integers(0, 10, n).astype(np.int64)
     finals = []
     ops.set_deterministic(True)
     try:
         for force in (False, True):
             params, model, agent = build_agent(cfg)
+            assert (agent.epoch, agent.mem_iters) == (epoch, mem_iters)
             agent._force_autograd = force
             agent.train_learner(torch.from_numpy(x).to(cuda), y)
             torch.cuda.synchronize()
             finals.append((model.flat_params().cpu().numpy().copy(), agent.buffer.buffer_img.cpu().numpy().copy(),
-                           agent.buffer.buffer_label.cpu().numpy().copy(), agent.buffer.n_seen_so_far,
-                           {k: v.cpu().numpy().copy() for k, v in model.state_dict().items() if "running" in k}))
+                           agent.buffer.buffer_label.cpu().numpy().copy(), agent.buffer.n_seen_so_far, _bn_state(model)))
     finally:
         ops.set_deterministic(False)
     (w1, b1, l1, n1, r1), (w0, b0, l0, n0, r0) = finals
-    assert n1 == n0 == 600 and np.array_equal(l1, l0) and np.array_equal(b1, b0)
+    assert n1 == n0 == epoch * n and np.array_equal(l1, l0) and np.array_equal(b1, b0)
     assert np.array_equal(w1, w0)
-    for k in r0:
-        assert np.array_equal(r1[k], r0[k]), k
+    _assert_bn_state(r1, r0)
 
 
 def test_aser_combined_pass_direct_backward_is_schedule_only(cuda):
@@ -588,26 +649,29 @@ def test_aser_pipelined_loop_is_schedule_only(cuda, monkeypatch):
     for the ranking, class table, row moves).  Same kernels on the same data, same RNG draws: 40 free-running ER + ASER steps
     (memory filling up, then Shapley-ranked replacement and retrieval) with and without the pipelining must end in the same replay
     memory, class table and counters exactly, and the same weights up to the order of the fp64 statistic atomics."""
+    aser_pipelined_loop_legs(cuda, monkeypatch, 1, 1, 400)
+
+
+def aser_pipelined_loop_legs(cuda, monkeypatch, epoch, mem_iters, n):
     from ocl_amd.plugins.buffer_utils import ClassBalancedRandomSampling as CBRS
-    cfg = dict(STEP_CASES["aser_c100"])
+    cfg = dict(STEP_CASES["aser_c100"], epoch=epoch, mem_iters=mem_iters)
     rng = np.random.default_rng(78)
-    x = rng.integers(0, 256, (400, 32, 32, 3), dtype=np.uint8)
-    y = rng.integers(0, 8, 400).astype(np.int64)
+    x = rng.integers(0, 256, (n, 32, 32, 3), dtype=np.uint8)
+    y = rng.integers(0, 8, n).astype(np.int64)
     finals = []
     for flag in ("1", "0"):
         monkeypatch.setenv("OCL_ASER_PIPELINE", flag)
         params, model, agent = build_agent(cfg)
+        assert (agent.epoch, agent.mem_iters) == (epoch, mem_iters)
         agent.train_learner(torch.from_numpy(x).to(cuda), y)
         torch.cuda.synchronize()
         table = {int(k): sorted(v) for k, v in CBRS.class_index_cache.items()}
         finals.append((model.flat_params().cpu().numpy().copy(), agent.buffer.buffer_img.cpu().numpy().copy(),
-                       agent.buffer.buffer_label.cpu().numpy().copy(), agent.buffer.n_seen_so_far, table,
-                       {k: v.cpu().numpy().copy() for k, v in model.state_dict().items() if "running" in k}))
+                       agent.buffer.buffer_label.cpu().numpy().copy(), agent.buffer.n_seen_so_far, table, _bn_state(model)))
     (w1, b1, l1, n1, t1, r1), (w0, b0, l0, n0, t0, r0) = finals
-    assert n1 == n0 == 400 and np.array_equal(l1, l0) and np.array_equal(b1, b0) and t1 == t0
+    assert n1 == n0 == epoch * n and np.array_equal(l1, l0) and np.array_equal(b1, b0) and t1 == t0
     assert np.abs(w1 - w0).max() < 1e-4 * max(1.0, np.abs(w0).max())
-    for k in r0:
-        assert np.abs(r1[k] - r0[k]).max() < 1e-4 * max(1.0, np.abs(r0[k]).max()), k
+    _assert_bn_state(r1, r0, rel=1e-4)
 
 
 def test_aser_passes_without_readers_are_schedule_only(cuda):
@@ -618,31 +682,34 @@ def test_aser_passes_without_readers_are_schedule_only(cuda):
     forwards under autograd + both losses, as the co-simulations run it), with order-independent batch sums: 40 free-running steps
     (memory filling up, then Shapley-ranked replacement and retrieval) end in the same weights, running statistics, replay memory,
     class table and counters BIT FOR BIT."""
+    aser_passes_without_readers_legs(cuda, 1, 1, 400)
+
+
+def aser_passes_without_readers_legs(cuda, epoch, mem_iters, n):
     from ocl_amd import ops
     from ocl_amd.plugins.buffer_utils import ClassBalancedRandomSampling as CBRS
-    cfg = dict(STEP_CASES["aser_c100"])
+    cfg = dict(STEP_CASES["aser_c100"], epoch=epoch, mem_iters=mem_iters)
     rng = np.random.default_rng(77)
-    x = rng.integers(0, 256, (400, 32, 32, 3), dtype=np.uint8)
-    y = rng.integers(0, 8, 400).astype(np.int64)
+    x = rng.integers(0, 256, (n, 32, 32, 3), dtype=np.uint8)
+    y = rng.integers(0, 8, n).astype(np.int64)
     finals = []
     ops.set_deterministic(True)
     try:
         for force in (False, True):
             params, model, agent = build_agent(cfg)
+            assert (agent.epoch, agent.mem_iters) == (epoch, mem_iters)
             agent._force_losses = force
             agent.train_learner(torch.from_numpy(x).to(cuda), y)
             torch.cuda.synchronize()
             table = {int(k): sorted(v) for k, v in CBRS.class_index_cache.items()}
             finals.append((model.flat_params().cpu().numpy().copy(), agent.buffer.buffer_img.cpu().numpy().copy(),
-                           agent.buffer.buffer_label.cpu().numpy().copy(), agent.buffer.n_seen_so_far, table,
-                           {k: v.cpu().numpy().copy() for k, v in model.state_dict().items() if "running" in k or "num_batches" in k}))
+                           agent.buffer.buffer_label.cpu().numpy().copy(), agent.buffer.n_seen_so_far, table, _bn_state(model)))
     finally:
         ops.set_deterministic(False)
     (w1, b1, l1, n1, t1, r1), (w0, b0, l0, n0, t0, r0) = finals
-    assert n1 == n0 == 400 and np.array_equal(l1, l0) and np.array_equal(b1, b0) and t1 == t0
+    assert n1 == n0 == epoch * n and np.array_equal(l1, l0) and np.array_equal(b1, b0) and t1 == t0
     assert np.array_equal(w1, w0)
-    for k in r0:
-        assert np.array_equal(r1[k], r0[k]), k
+    _assert_bn_state(r1, r0)
 
 
 def test_kd_trick_teacher_and_combined_loss_vs_oracle(cuda):

@@ -63,6 +63,11 @@ int upload_small(const void* host, size_t nbytes, void* dev, hipStream_t s);
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+// [a, a + na) and [b, b + nb) share a byte
+static inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
 
 }  // namespace ocl
 

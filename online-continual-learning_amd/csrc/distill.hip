@@ -140,12 +140,6 @@ __global__ void __launch_bounds__(256) ce_kd_blend_kernel(const float* __restric
     }
 }
 
-// [a, a + na) and [b, b + nb) share a byte
-static inline bool blend_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 int ocl_ce_kd_blend_fwd_bwd(const float* logits, const int64_t* y, const float* teacher, int n, int c, float T, float w_new, float w_old,
                             float* loss_out, float* dlogits, void* stream) {
     OCL_REQUIRE(logits && y && loss_out, "ce_kd_blend: null pointer (logits, y and loss_out are required)");
@@ -154,8 +148,8 @@ int ocl_ce_kd_blend_fwd_bwd(const float* logits, const int64_t* y, const float* 
     OCL_REQUIRE(std::isfinite(w_new) && std::isfinite(w_old), "ce_kd_blend: weights %g, %g (must be finite)", (double)w_new, (double)w_old);
     const size_t bytes = (size_t)n * (size_t)c * sizeof(float);
     if (dlogits) {
-        OCL_REQUIRE(!blend_overlap(dlogits, bytes, logits, bytes), "ce_kd_blend: dlogits overlaps logits");
-        OCL_REQUIRE(!(teacher && blend_overlap(dlogits, bytes, teacher, bytes)), "ce_kd_blend: dlogits overlaps teacher");
+        OCL_REQUIRE(!ranges_overlap(dlogits, bytes, logits, bytes), "ce_kd_blend: dlogits overlaps logits");
+        OCL_REQUIRE(!(teacher && ranges_overlap(dlogits, bytes, teacher, bytes)), "ce_kd_blend: dlogits overlaps teacher");
     }
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_HEAD, s);

@@ -109,12 +109,6 @@ __global__ void __launch_bounds__(256) bce_distill_kernel(const float* __restric
     }
 }
 
-// [a, a + na) and [b, b + nb) share a byte
-static inline bool bce_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 int ocl_bce_distill_fwd_bwd(const float* logits, const float* teacher, const int64_t* pos, int n, int n_stream, int c, int n_cls, int n_old,
                             float* loss_out, float* dlogits, void* stream) {
     OCL_REQUIRE(logits && pos && loss_out, "bce_distill: null pointer (logits, pos and loss_out are required)");
@@ -124,9 +118,9 @@ int ocl_bce_distill_fwd_bwd(const float* logits, const float* teacher, const int
     OCL_REQUIRE(teacher || n_old == 0, "bce_distill: n_old=%d without a teacher (a null teacher requires n_old == 0)", n_old);
     const size_t bytes = (size_t)n * (size_t)c * sizeof(float);
     if (dlogits) {
-        OCL_REQUIRE(!bce_overlap(dlogits, bytes, logits, bytes), "bce_distill: dlogits overlaps logits");
-        OCL_REQUIRE(!(teacher && bce_overlap(dlogits, bytes, teacher, bytes)), "bce_distill: dlogits overlaps teacher");
-        OCL_REQUIRE(!bce_overlap(dlogits, bytes, pos, (size_t)n_stream * sizeof(int64_t)), "bce_distill: dlogits overlaps pos");
+        OCL_REQUIRE(!ranges_overlap(dlogits, bytes, logits, bytes), "bce_distill: dlogits overlaps logits");
+        OCL_REQUIRE(!(teacher && ranges_overlap(dlogits, bytes, teacher, bytes)), "bce_distill: dlogits overlaps teacher");
+        OCL_REQUIRE(!ranges_overlap(dlogits, bytes, pos, (size_t)n_stream * sizeof(int64_t)), "bce_distill: dlogits overlaps pos");
     }
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_HEAD, s);

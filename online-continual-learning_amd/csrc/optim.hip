@@ -1,7 +1,7 @@
 // K8b: torch.optim.Adam over the flat parameter array as one kernel.  HBM-bound fp32 streaming like sgd_flat (small_ops.hip): four
 // 16-byte loads (p, g, m, v) and three stores (p, m, v) per four elements, 28 bytes per element; no LDS, no atomics, no reduction.
 // IEEE sqrtf and '/' (the compiler's default): nothing in this file may be built with fast-math or replaced by an approximation.
-#include "common.h"
+#include "flat_dev.h"
 #include <math.h>
 
 using namespace ocl;
@@ -23,51 +23,34 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
 }
 
 // elements [skip_begin, skip_end) keep p, m and v (parameters that never get a gradient: torch skips a tensor whose .grad is None)
-__global__ void __launch_bounds__(256) adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+__global__ void __launch_bounds__(FLAT_THREADS) adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, int64_t n, AdamStep c, int64_t skip_begin, int64_t skip_end) {
-    const int64_t n4 = n >> 2;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    float4* p4 = (float4*)p;
-    const float4* g4 = (const float4*)g;
-    float4* m4 = (float4*)m;
-    float4* v4 = (float4*)v;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const int64_t e = i << 2;
-        if (e >= skip_begin && e + 4 <= skip_end) continue;   // wholly inside the range: neither read nor written
-        const float4 a = p4[i], b = g4[i], mo = m4[i], vo = v4[i];
-        float4 pn = a, mn = mo, vn = vo;
-        adam_one(pn.x, b.x, mn.x, vn.x, c);
-        adam_one(pn.y, b.y, mn.y, vn.y, c);
-        adam_one(pn.z, b.z, mn.z, vn.z, c);
-        adam_one(pn.w, b.w, mn.w, vn.w, c);
-        if (e + 3 >= skip_begin && e < skip_end) {   // a boundary of the range falls into this vector: per-element choice
-            const bool s0 = e >= skip_begin && e < skip_end, s1 = e + 1 >= skip_begin && e + 1 < skip_end;
-            const bool s2 = e + 2 >= skip_begin && e + 2 < skip_end, s3 = e + 3 >= skip_begin && e + 3 < skip_end;
-            pn.x = s0 ? a.x : pn.x; mn.x = s0 ? mo.x : mn.x; vn.x = s0 ? vo.x : vn.x;
-            pn.y = s1 ? a.y : pn.y; mn.y = s1 ? mo.y : mn.y; vn.y = s1 ? vo.y : vn.y;
-            pn.z = s2 ? a.z : pn.z; mn.z = s2 ? mo.z : mn.z; vn.z = s2 ? vo.z : vn.z;
-            pn.w = s3 ? a.w : pn.w; mn.w = s3 ? mo.w : mn.w; vn.w = s3 ? vo.w : vn.w;
+    flat_for_each(n, [&](auto at) {
+        constexpr int W = decltype(at)::W;
+        const int64_t e = at.e;
+        if (e >= skip_begin && e + W <= skip_end) return;   // wholly inside the range: neither read nor written
+        const auto po = at.load(p), b = at.load(g), mo = at.load(m), vo = at.load(v);
+        auto pn = po, mn = mo, vn = vo;
+#pragma unroll
+        for (int k = 0; k < W; ++k) adam_one(pn[k], b[k], mn[k], vn[k], c);
+        if (e + W - 1 >= skip_begin && e < skip_end) {   // a boundary of the range falls into this vector: per-element choice
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                const bool skip = e + k >= skip_begin && e + k < skip_end;
+                pn[k] = skip ? po[k] : pn[k];
+                mn[k] = skip ? mo[k] : mn[k];
+                vn[k] = skip ? vo[k] : vn[k];
+            }
         }
-        p4[i] = pn;
-        m4[i] = mn;
-        v4[i] = vn;
-    }
-    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (i >= skip_begin && i < skip_end) continue;
-        float pn = p[i], mn = m[i], vn = v[i];
-        adam_one(pn, g[i], mn, vn, c);
-        p[i] = pn;
-        m[i] = mn;
-        v[i] = vn;
-    }
+        at.store(p, pn);
+        at.store(m, mn);
+        at.store(v, vn);
+    });
 }
 
 int ocl_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, float grad_scale, int64_t step, int64_t skip_begin, int64_t skip_end, void* stream) {
-    OCL_REQUIRE(params && grads && exp_avg && exp_avg_sq, "adam: null pointer");
-    OCL_REQUIRE(n > 0, "adam: n=%lld (must be > 0)", (long long)n);
-    OCL_REQUIRE((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16) == 0,
-                "adam: pointers must be 16-B aligned");
+    if (int rc = flat_check_args("adam", n, {{params, "params"}, {grads, "grads"}, {exp_avg, "exp_avg"}, {exp_avg_sq, "exp_avg_sq"}})) return rc;
     OCL_REQUIRE(step >= 1, "adam: step=%lld (1-based)", (long long)step);
     OCL_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "adam: betas (%g, %g) outside [0, 1)", beta1, beta2);
     OCL_REQUIRE(eps >= 0.f, "adam: eps=%g (must be >= 0)", eps);
@@ -86,10 +69,10 @@ int ocl_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
     c.gs = grad_scale;
     c.step_size = (float)((double)lr / (1.0 - pow(b1, (double)step)));
     c.bc2_sqrt = (float)sqrt(1.0 - pow(b2, (double)step));
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(2048, ((n >> 2) + 255) / 256));
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(2048, ((n >> 2) + FLAT_THREADS - 1) / FLAT_THREADS));
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_BN, s);
-    hipLaunchKernelGGL(adam_flat_kernel, dim3(blocks), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, n, c, skip_begin, skip_end);
+    hipLaunchKernelGGL(adam_flat_kernel, dim3(blocks), dim3(FLAT_THREADS), 0, s, params, grads, exp_avg, exp_avg_sq, n, c, skip_begin, skip_end);
     OCL_LAUNCH_CHECK();
     return OCL_OK;
 }

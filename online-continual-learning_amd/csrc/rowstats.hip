@@ -88,12 +88,6 @@ __global__ void __launch_bounds__(64 * RS_ROWS) row_argmax_groupsum_kernel(const
     }
 }
 
-// [a, a + na) and [b, b + nb) share a byte
-static inline bool rs_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 int ocl_row_argmax_groupsum(const float* x, int n, int c, const int32_t* col_group, int sel, int64_t* argmax_out, double* sum_out,
                             void* stream) {
     OCL_REQUIRE(x, "row_argmax_groupsum: null pointer (x is required)");
@@ -102,14 +96,14 @@ int ocl_row_argmax_groupsum(const float* x, int n, int c, const int32_t* col_gro
     const size_t x_bytes = (size_t)n * (size_t)c * sizeof(float), g_bytes = (size_t)c * sizeof(int32_t);
     const size_t a_bytes = (size_t)n * sizeof(int64_t), s_bytes = (size_t)n * sizeof(double);
     if (argmax_out) {
-        OCL_REQUIRE(!rs_overlap(argmax_out, a_bytes, x, x_bytes), "row_argmax_groupsum: argmax_out overlaps x");
-        OCL_REQUIRE(!(col_group && rs_overlap(argmax_out, a_bytes, col_group, g_bytes)), "row_argmax_groupsum: argmax_out overlaps col_group");
+        OCL_REQUIRE(!ranges_overlap(argmax_out, a_bytes, x, x_bytes), "row_argmax_groupsum: argmax_out overlaps x");
+        OCL_REQUIRE(!(col_group && ranges_overlap(argmax_out, a_bytes, col_group, g_bytes)), "row_argmax_groupsum: argmax_out overlaps col_group");
     }
     if (sum_out) {
-        OCL_REQUIRE(!rs_overlap(sum_out, s_bytes, x, x_bytes), "row_argmax_groupsum: sum_out overlaps x");
-        OCL_REQUIRE(!(col_group && rs_overlap(sum_out, s_bytes, col_group, g_bytes)), "row_argmax_groupsum: sum_out overlaps col_group");
+        OCL_REQUIRE(!ranges_overlap(sum_out, s_bytes, x, x_bytes), "row_argmax_groupsum: sum_out overlaps x");
+        OCL_REQUIRE(!(col_group && ranges_overlap(sum_out, s_bytes, col_group, g_bytes)), "row_argmax_groupsum: sum_out overlaps col_group");
     }
-    OCL_REQUIRE(!(argmax_out && sum_out && rs_overlap(argmax_out, a_bytes, sum_out, s_bytes)), "row_argmax_groupsum: argmax_out overlaps sum_out");
+    OCL_REQUIRE(!(argmax_out && sum_out && ranges_overlap(argmax_out, a_bytes, sum_out, s_bytes)), "row_argmax_groupsum: argmax_out overlaps sum_out");
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_HEAD, s);
     auto k = c <= RS_REG * 64 ? row_argmax_groupsum_kernel<true> : row_argmax_groupsum_kernel<false>;

@@ -1,7 +1,7 @@
 // K6-K13 + K9: buffer gather/scatter, SGD, CE, SupCon, kNN-Shapley, sort, NCM, MIR score, augmentation,
 // small MFMA GEMM.  HBM/latency-bound integer+fp32 work: coalesced 16-B accesses, LDS sorts, one
 // workgroup per row — none of this is reshaped into GEMMs.
-#include "common.h"
+#include "flat_dev.h"
 #include <math.h>
 
 using namespace ocl;
@@ -187,23 +187,14 @@ __global__ void __launch_bounds__(256) gather_u8_hwc_f32_chw(const uint8_t* __re
 // =====================================================================================================
 __global__ void __launch_bounds__(256) sgd_flat(float* __restrict__ p, const float* __restrict__ g, int64_t n, float lr,
                                                 float wd, float gs, float* __restrict__ out) {
-    const int64_t n4 = n >> 2;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    float4* o4 = (float4*)(out ? out : p);
-    const float4* p4 = (const float4*)p;
-    const float4* g4 = (const float4*)g;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float4 a = p4[i], b = g4[i];
-        float4 r;
-        r.x = fmaf(-lr, fmaf(wd, a.x, b.x * gs), a.x);
-        r.y = fmaf(-lr, fmaf(wd, a.y, b.y * gs), a.y);
-        r.z = fmaf(-lr, fmaf(wd, a.z, b.z * gs), a.z);
-        r.w = fmaf(-lr, fmaf(wd, a.w, b.w * gs), a.w);
-        o4[i] = r;
-    }
     float* o = out ? out : p;
-    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        o[i] = fmaf(-lr, fmaf(wd, p[i], g[i] * gs), p[i]);
+    flat_for_each(n, [&](auto at) {
+        auto a = at.load(p);
+        const auto b = at.load(g);
+#pragma unroll
+        for (int k = 0; k < at.W; ++k) a[k] = fmaf(-lr, fmaf(wd, a[k], b[k] * gs), a[k]);
+        at.store(o, a);
+    });
 }
 
 // =====================================================================================================

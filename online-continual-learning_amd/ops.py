@@ -148,6 +148,29 @@ def gather_f32_images(task_f32_nhwc, idx):
     return out
 
 
+# ---- K8, K8b-e: the flat-array kernels (csrc/flat_dev.h) ------------------------------------------------
+def _flat_check(msg, first, *rest):
+    """float32 arrays of one length on one GPU (a None among `rest` is skipped): returns the length, or raises RuntimeError(msg)."""
+    n = first.numel()
+    for t in (first,) + rest:
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_cuda or t.device != first.device):
+            raise RuntimeError(msg)
+    return n
+
+
+def _flat_workspace(cache, doubles, msg, first, n, workspace):
+    """The float64 workspace of one operation: the caller's, checked (RuntimeError(msg)), or the one of (device, n) in `cache`,
+    allocated once with doubles(n) elements.  Every operation has a cache of its own: no two share a workspace."""
+    if workspace is None:
+        key = (first.device.index, n)
+        workspace = cache.get(key)
+        if workspace is None:
+            workspace = cache[key] = torch.empty(doubles(n), dtype=torch.float64, device=first.device)
+    elif workspace.dtype != torch.float64 or workspace.device != first.device:
+        raise RuntimeError(msg)
+    return workspace
+
+
 # ---- K8 ----------------------------------------------------------------------------------------------
 def sgd_step(params_flat, grads_flat, lr, weight_decay=0.0, grad_scale=1.0, out=None):
     ffi.init()
@@ -162,10 +185,8 @@ def adam_step(params_flat, grads_flat, exp_avg, exp_avg_sq, step, lr, betas=(0.9
     """One torch.optim.Adam step (amsgrad off) over the flat arrays, in place; `step` is this step's 1-based number, elements
     skip[0] .. skip[1] - 1 are left untouched."""
     ffi.init()
-    for t in (grads_flat, exp_avg, exp_avg_sq):
-        if t.dtype != torch.float32 or params_flat.dtype != torch.float32 or t.numel() != params_flat.numel() or t.device != params_flat.device:
-            raise RuntimeError("adam_step: four float32 arrays of one length on one device")
-    ffi.check(ffi.lib().ocl_adam_step(ffi.ptr(params_flat), ffi.ptr(grads_flat), ffi.ptr(exp_avg), ffi.ptr(exp_avg_sq), params_flat.numel(),
+    n = _flat_check("adam_step: four float32 arrays of one length on one device", params_flat, grads_flat, exp_avg, exp_avg_sq)
+    ffi.check(ffi.lib().ocl_adam_step(ffi.ptr(params_flat), ffi.ptr(grads_flat), ffi.ptr(exp_avg), ffi.ptr(exp_avg_sq), n,
                                       float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale),
                                       int(step), int(skip[0]), int(skip[1]), ffi.stream()), "adam_step")
     return params_flat
@@ -180,17 +201,9 @@ def agem_project(g, g_ref_inout, workspace=None, info=None):
     else a copy of g; returns g_ref_inout.  workspace: a float64 tensor of ocl_agem_workspace_doubles(n) elements (default: one per
     (device, n), allocated once); info: a float32 tensor of 4 that receives prod, prod_ref, the coefficient and the decision."""
     ffi.init()
-    n = g.numel()
-    if (g.dtype != torch.float32 or g_ref_inout.dtype != torch.float32 or g_ref_inout.numel() != n or not g.is_cuda
-            or g.device != g_ref_inout.device):
-        raise RuntimeError("agem_project: two float32 arrays of one length on one GPU")
-    if workspace is None:
-        key = (g.device.index, n)
-        workspace = _agem_workspaces.get(key)
-        if workspace is None:
-            workspace = _agem_workspaces[key] = torch.empty(ffi.lib().ocl_agem_workspace_doubles(n), dtype=torch.float64, device=g.device)
-    elif workspace.dtype != torch.float64 or workspace.device != g.device:
-        raise RuntimeError("agem_project: the workspace is a float64 tensor on the gradients' device")
+    n = _flat_check("agem_project: two float32 arrays of one length on one GPU", g, g_ref_inout)
+    workspace = _flat_workspace(_agem_workspaces, ffi.lib().ocl_agem_workspace_doubles,
+                                "agem_project: the workspace is a float64 tensor on the gradients' device", g, n, workspace)
     if info is not None and (info.dtype != torch.float32 or info.numel() < 4 or info.device != g.device):
         raise RuntimeError("agem_project: info is a float32 tensor of 4 on the gradients' device")
     ffi.check(ffi.lib().ocl_agem_project(ffi.ptr(g), ffi.ptr(g_ref_inout), n, ffi.ptr(workspace), workspace.numel(), ffi.ptr(info),
@@ -210,17 +223,12 @@ def clip_grad_norm_(grads_flat, max_norm, workspace=None, info=None):
     (default: one per (device, n), allocated once); info: a float32 tensor of at least 4 that receives the total norm, the coefficient
     (1.0 when nothing was clipped), the decision and sum g * g (default: one per device, allocated once)."""
     ffi.init()
-    n = grads_flat.numel()
-    if grads_flat.dtype != torch.float32 or not grads_flat.is_cuda or not grads_flat.is_contiguous():
+    n = _flat_check("clip_grad_norm_: a contiguous float32 array on the GPU", grads_flat)
+    if not grads_flat.is_contiguous():
         raise RuntimeError("clip_grad_norm_: a contiguous float32 array on the GPU")
     dev = grads_flat.device
-    if workspace is None:
-        key = (dev.index, n)
-        workspace = _clip_workspaces.get(key)
-        if workspace is None:
-            workspace = _clip_workspaces[key] = torch.empty(ffi.lib().ocl_clip_workspace_doubles(n), dtype=torch.float64, device=dev)
-    elif workspace.dtype != torch.float64 or workspace.device != dev:
-        raise RuntimeError("clip_grad_norm_: the workspace is a float64 tensor on the gradients' device")
+    workspace = _flat_workspace(_clip_workspaces, ffi.lib().ocl_clip_workspace_doubles,
+                                "clip_grad_norm_: the workspace is a float64 tensor on the gradients' device", grads_flat, n, workspace)
     if info is None:
         info = _clip_infos.get(dev.index)
         if info is None:
@@ -236,23 +244,9 @@ def clip_grad_norm_(grads_flat, max_norm, workspace=None, info=None):
 _ewc_workspaces = {}
 
 
-def _ewc_check(what, first, *rest):
-    n = first.numel()
-    for t in (first,) + rest:
-        if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_cuda or t.device != first.device):
-            raise RuntimeError("%s: float32 arrays of one length on one GPU" % what)
-    return n
-
-
 def _ewc_workspace(what, first, n, workspace):
-    if workspace is None:
-        key = (first.device.index, n)
-        workspace = _ewc_workspaces.get(key)
-        if workspace is None:
-            workspace = _ewc_workspaces[key] = torch.empty(ffi.lib().ocl_ewc_workspace_doubles(n), dtype=torch.float64, device=first.device)
-    elif workspace.dtype != torch.float64 or workspace.device != first.device:
-        raise RuntimeError("%s: the workspace is a float64 tensor on the arrays' device" % what)
-    return workspace
+    return _flat_workspace(_ewc_workspaces, ffi.lib().ocl_ewc_workspace_doubles,
+                           "%s: the workspace is a float64 tensor on the arrays' device" % what, first, n, workspace)
 
 
 def ewc_accumulate(grads_inout, tmp_fisher_inout, params, prev_params=None, fisher_hat=None, scale=0.0, workspace=None, penalty_out=None):
@@ -263,7 +257,7 @@ def ewc_accumulate(grads_inout, tmp_fisher_inout, params, prev_params=None, fish
     ffi.init()
     if (prev_params is None) != (fisher_hat is None):
         raise RuntimeError("ewc_accumulate: prev_params and fisher_hat are given together or not at all")
-    n = _ewc_check("ewc_accumulate", grads_inout, tmp_fisher_inout, params, prev_params, fisher_hat)
+    n = _flat_check("ewc_accumulate: float32 arrays of one length on one GPU", grads_inout, tmp_fisher_inout, params, prev_params, fisher_hat)
     if penalty_out is not None:
         if penalty_out.dtype != torch.float32 or penalty_out.numel() < 1 or penalty_out.device != grads_inout.device:
             raise RuntimeError("ewc_accumulate: penalty_out is a float32 tensor of 1 on the arrays' device")
@@ -280,7 +274,7 @@ def ewc_accumulate(grads_inout, tmp_fisher_inout, params, prev_params=None, fish
 def ewc_fisher_ema(running_inout, tmp_inout, keep, gain):
     """running = keep * running + gain * tmp in float32 with separately rounded products (agents/ewc_pp.py:97-100), then tmp = 0 (:102)."""
     ffi.init()
-    n = _ewc_check("ewc_fisher_ema", running_inout, tmp_inout)
+    n = _flat_check("ewc_fisher_ema: float32 arrays of one length on one GPU", running_inout, tmp_inout)
     ffi.check(ffi.lib().ocl_ewc_fisher_ema(ffi.ptr(running_inout), ffi.ptr(tmp_inout), n, float(keep), float(gain), ffi.stream()),
               "ewc_fisher_ema")
     return running_inout
@@ -290,7 +284,7 @@ def ewc_fisher_normalize(running, fisher_hat_out, workspace=None, minmax_out=Non
     """fisher_hat_out = (running - min) / (max - min + 1e-32) over the whole array in IEEE float32 (agents/ewc_pp.py:76-80), two
     launches; minmax_out: a float32 tensor of 2 that receives min and max.  Returns fisher_hat_out."""
     ffi.init()
-    n = _ewc_check("ewc_fisher_normalize", running, fisher_hat_out)
+    n = _flat_check("ewc_fisher_normalize: float32 arrays of one length on one GPU", running, fisher_hat_out)
     workspace = _ewc_workspace("ewc_fisher_normalize", running, n, workspace)
     if minmax_out is not None and (minmax_out.dtype != torch.float32 or minmax_out.numel() < 2 or minmax_out.device != running.device):
         raise RuntimeError("ewc_fisher_normalize: minmax_out is a float32 tensor of 2 on the arrays' device")

@@ -154,6 +154,21 @@ def test_abi_refuses_a_misaligned_pointer_without_a_device():
         assert rc == OCL_ERR_ARG and "aligned" in msg, (name, rc, msg)
 
 
+def test_abi_refuses_overlapping_arrays_without_a_device():
+    """params, grads, exp_avg and exp_avg_sq are four disjoint arrays: an aliased pair would be read and written by different
+    threads in no order."""
+    buf = (C.c_float * 64)()
+    a = (C.addressof(buf) + 15) // 16 * 16
+    arrays = dict(params=a, grads=a + 256, exp_avg=a + 512, exp_avg_sq=a + 768)     # n = 16: 64 bytes each
+    for over in (dict(exp_avg=a),                  # exp_avg on params
+                 dict(exp_avg_sq=a + 256 - 16),    # exp_avg_sq ending inside grads
+                 dict(grads=a + 48)):              # grads starting inside params
+        rc, msg = _call(**dict(arrays, n=16, **over))
+        assert rc == OCL_ERR_ARG and msg.startswith("adam:") and "overlap" in msg, (over, rc, msg)
+    rc, msg = _call(**dict(arrays, n=16, step=0))                                   # the arrays themselves are accepted
+    assert rc == OCL_ERR_ARG and "step" in msg, (rc, msg)
+
+
 # ---- the float64 reference against torch ---------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("wd", [0.0, 1e-4])

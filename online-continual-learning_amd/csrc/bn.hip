@@ -21,7 +21,7 @@ __global__ void __launch_bounds__(256) bn_fwd_kernel(const BnFwdArgs a) {
     const double M = (double)a.m_per_group;
     for (int c = tid; c < a.C; c += 256) {
         double mean, var;
-        bn_batch_moments(a.stats, a.stat_rep_stride, g, c, a.C, M, a.eps, mean, var);
+        bn_batch_moments(a.stats, a.stat_rep_stride, g, c, a.C, M, mean, var);
         if (a.frozen_mean) {   // eval-mode BatchNorm on the tape: the running statistics, folded exactly as bn_fold_kernel does
             mean = (double)a.frozen_mean[c];
             var = (double)a.frozen_var[c];
@@ -34,13 +34,13 @@ __global__ void __launch_bounds__(256) bn_fwd_kernel(const BnFwdArgs a) {
         }
     }
     if (blockIdx.x == 0 && g == 0 && a.running_mean)
-        bn_running_update(a.stats, a.stat_rep_stride, a.G, a.C, M, a.momentum, a.eps, a.running_mean, a.running_var, a.nbt, tid, 256);
+        bn_running_update(a.stats, a.stat_rep_stride, a.G, a.C, M, a.momentum, a.running_mean, a.running_var, a.nbt, tid, 256);
     float* scb = sm + 2 * a.C;
     float* shb = sm + 3 * a.C;
     if (a.yb) {   // the projection shortcut's BatchNorm: the same table, statistics and running update from its own arena
         for (int c = tid; c < a.C; c += 256) {
             double mean, var;
-            bn_batch_moments(a.stats_b, a.stat_rep_stride, g, c, a.C, M, a.eps, mean, var);
+            bn_batch_moments(a.stats_b, a.stat_rep_stride, g, c, a.C, M, mean, var);
             if (a.frozen_mean_b) {
                 mean = (double)a.frozen_mean_b[c];
                 var = (double)a.frozen_var_b[c];
@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(256) bn_fwd_kernel(const BnFwdArgs a) {
             }
         }
         if (blockIdx.x == 0 && g == 0 && a.running_mean_b)
-            bn_running_update(a.stats_b, a.stat_rep_stride, a.G, a.C, M, a.momentum, a.eps, a.running_mean_b, a.running_var_b, a.nbt_b, tid, 256);
+            bn_running_update(a.stats_b, a.stat_rep_stride, a.G, a.C, M, a.momentum, a.running_mean_b, a.running_var_b, a.nbt_b, tid, 256);
     }
     __syncthreads();
     const int C4 = a.C >> 2;

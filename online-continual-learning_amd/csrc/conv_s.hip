@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(256, NT == 1 ? 5 : 4) conv_s_kernel(const Conv
         for (int j = (lead ? 0 : d1.y * C) + tid; j < j_end; j += 256) {
             const int gq = j / C, c = j - gq * C;
             double mean, var;
-            bn_batch_moments<2, FXM>(a.xf_stats, a.xf_rep_stride, gq, c, C, M, a.xf_eps, mean, var);
+            bn_batch_moments<2, FXM>(a.xf_stats, a.xf_rep_stride, gq, c, C, M, mean, var);
             const double xv = var + (double)a.xf_eps;
             double invstd = (double)rsqrtf((float)xv);
             invstd = invstd * (1.5 - 0.5 * xv * invstd * invstd);
@@ -123,7 +123,7 @@ __global__ void __launch_bounds__(256, NT == 1 ? 5 : 4) conv_s_kernel(const Conv
             }
         }
         if (lead && a.xf_running_mean)
-            bn_running_update<FXM>(a.xf_stats, a.xf_rep_stride, a.groups, C, M, a.xf_momentum, a.xf_eps, a.xf_running_mean, a.xf_running_var, a.xf_nbt, tid, 256);
+            bn_running_update<FXM>(a.xf_stats, a.xf_rep_stride, a.groups, C, M, a.xf_momentum, a.xf_running_mean, a.xf_running_var, a.xf_nbt, tid, 256);
     }
     stamp(1);
     const int nr = a.Qpad >> 2;                      // rounds of 4 groups; a multiple of 4 (the planner pads with zero-weight groups)

@@ -162,8 +162,8 @@ __device__ __forceinline__ double fx_total_atomic(const StatCell* cells, int64_t
 
 // mean / invstd of (group g, channel c) from the replicated batch sums (biased variance, nn.BatchNorm2d's normalisation)
 template <int B = 2 * kStatReps, int MODE = -1>   // replica loads in flight (see fx_total)
-__device__ __forceinline__ void bn_batch_moments(const StatCell* __restrict__ stats, int64_t rep_stride, int g, int c, int C, double M, float eps,
-                                                 double& mean, double& var) {
+__device__ __forceinline__ void bn_batch_moments(const StatCell* __restrict__ stats, int64_t rep_stride, int g, int c, int C, double M, double& mean,
+                                                 double& var) {
     double s1, s2;
     if constexpr (B >= 2 * kStatReps) {
         fx_total2(stats, rep_stride, ((int64_t)g * 2 + 0) * C + c, ((int64_t)g * 2 + 1) * C + c, s1, s2);
@@ -174,18 +174,17 @@ __device__ __forceinline__ void bn_batch_moments(const StatCell* __restrict__ st
     mean = s1 / M;
     var = s2 / M - mean * mean;
     if (var < 0.0) var = 0.0;
-    (void)eps;
 }
 // running statistics: one update per group, in order (= the reference's separate forward calls), unbiased variance, momentum
 template <int MODE = -1>
 __device__ __forceinline__ void bn_running_update(const StatCell* __restrict__ stats, int64_t rep_stride, int G, int C, double M, float momentum,
-                                                  float eps, float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                  float* __restrict__ running_mean, float* __restrict__ running_var,
                                                   int64_t* __restrict__ nbt, int tid, int nthreads) {
     for (int c = tid; c < C; c += nthreads) {
         float rm = running_mean[c], rv = running_var[c];
         for (int gg = 0; gg < G; ++gg) {
             double mean, var;
-            bn_batch_moments<1, MODE>(stats, rep_stride, gg, c, C, M, eps, mean, var);   // (one workgroup per launch runs this: few loads in flight, few registers)
+            bn_batch_moments<1, MODE>(stats, rep_stride, gg, c, C, M, mean, var);   // (one workgroup per launch runs this: few loads in flight, few registers)
             const double unb = M > 1.0 ? var * M / (M - 1.0) : var;
             rm = momentum * (float)mean + (1.f - momentum) * rm;
             rv = momentum * (float)unb + (1.f - momentum) * rv;

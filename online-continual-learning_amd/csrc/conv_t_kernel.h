@@ -163,7 +163,7 @@ __global__ void __launch_bounds__(256, PIPE ? 1 : 2) conv_t_kernel(const ConvArg
         for (int j = tid; j < a.groups * C; j += 256) {
             const int gq = j / C, c = j - gq * C;
             double mean, var;
-            bn_batch_moments(a.xf_stats, a.xf_rep_stride, gq, c, C, M, a.xf_eps, mean, var);
+            bn_batch_moments(a.xf_stats, a.xf_rep_stride, gq, c, C, M, mean, var);
             // 1 / sqrt(var + eps) without the fp64 divide / square-root sequences (every workgroup of the launch runs this prologue):
             // fp32 rsqrt seed + two Newton steps in fp64 (relative error < 1e-15: the float it is rounded to is the exact one)
             const double xv = var + (double)a.xf_eps;
@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(256, PIPE ? 1 : 2) conv_t_kernel(const ConvArg
             }
         }
         if (lead && a.xf_running_mean)
-            bn_running_update(a.xf_stats, a.xf_rep_stride, a.groups, C, M, a.xf_momentum, a.xf_eps, a.xf_running_mean, a.xf_running_var, a.xf_nbt, tid, 256);
+            bn_running_update(a.xf_stats, a.xf_rep_stride, a.groups, C, M, a.xf_momentum, a.xf_running_mean, a.xf_running_var, a.xf_nbt, tid, 256);
     }
     if (BNB && (flags & EPI_BNB)) bnb_table(a, const_cast<float*>(bnt), tid, 256);
     if (tid < ntab) ctab[tid] = tab0;

@@ -241,7 +241,7 @@ __global__ void __launch_bounds__(256, 1) conv_w_kernel(const ConvArgs a) {
         for (int j = tid; j < a.groups * C; j += 256) {
             const int gq = j / C, c = j - gq * C;
             double mean, var;
-            bn_batch_moments(a.xf_stats, a.xf_rep_stride, gq, c, C, M, a.xf_eps, mean, var);
+            bn_batch_moments(a.xf_stats, a.xf_rep_stride, gq, c, C, M, mean, var);
             const double xv = var + (double)a.xf_eps;
             double invstd = (double)rsqrtf((float)xv);
             invstd = invstd * (1.5 - 0.5 * xv * invstd * invstd);
@@ -257,7 +257,7 @@ __global__ void __launch_bounds__(256, 1) conv_w_kernel(const ConvArgs a) {
             }
         }
         if (lead && a.xf_running_mean)
-            bn_running_update(a.xf_stats, a.xf_rep_stride, a.groups, C, M, a.xf_momentum, a.xf_eps, a.xf_running_mean, a.xf_running_var, a.xf_nbt, tid, 256);
+            bn_running_update(a.xf_stats, a.xf_rep_stride, a.groups, C, M, a.xf_momentum, a.xf_running_mean, a.xf_running_var, a.xf_nbt, tid, 256);
     }
     if (BNB && (flags & EPI_BNB)) bnb_table(a, const_cast<float*>(bnt), tid, 256);
     if (tid < a.Qpad) qoff[tid] = qtab;
@@ -667,7 +667,7 @@ __global__ void __launch_bounds__(256, 1) conv_wx_kernel(const ConvArgs a) {
         for (int j = tid; j < a.groups * C; j += 256) {
             const int gq = j / C, c = j - gq * C;
             double mean, var;
-            bn_batch_moments(a.xf_stats, a.xf_rep_stride, gq, c, C, M, a.xf_eps, mean, var);
+            bn_batch_moments(a.xf_stats, a.xf_rep_stride, gq, c, C, M, mean, var);
             const double xv = var + (double)a.xf_eps;
             double invstd = (double)rsqrtf((float)xv);
             invstd = invstd * (1.5 - 0.5 * xv * invstd * invstd);
@@ -683,7 +683,7 @@ __global__ void __launch_bounds__(256, 1) conv_wx_kernel(const ConvArgs a) {
             }
         }
         if (lead && a.xf_running_mean)
-            bn_running_update(a.xf_stats, a.xf_rep_stride, a.groups, C, M, a.xf_momentum, a.xf_eps, a.xf_running_mean, a.xf_running_var, a.xf_nbt, tid, 256);
+            bn_running_update(a.xf_stats, a.xf_rep_stride, a.groups, C, M, a.xf_momentum, a.xf_running_mean, a.xf_running_var, a.xf_nbt, tid, 256);
     }
     if (BNB && (flags & EPI_BNB)) bnb_table(a, const_cast<float*>(bnt), tid, 256);
     if (tid < a.Qpad) qoff[tid] = qtab;

@@ -96,6 +96,12 @@ def test_train_forward_backward_vs_oracle(cuda, agent, data, head, n, groups):
     gradient vs autograd on the oracle with the ReLU activation pattern teacher-forced to the engine's (a ReLU input
     within fp32 round-off of zero may land on either side — about one element per 10^5 — and the gradient is
     discontinuous there); every element whose pattern differs from ATen's must be such an ambiguous one."""
+    train_forward_backward_vs_oracle(cuda, agent, data, head, n, groups)
+
+
+def train_forward_backward_vs_oracle(cuda, agent, data, head, n, groups, images=None):
+    """The body of test_train_forward_backward_vs_oracle; images: [n, 3, hw, hw] float32 instead of the uniform ones (tests/test_gpu_bn_cond.py
+    runs the same assertions on ill-conditioned images)."""
     hw = 84 if data == "mini_imagenet" else 32
     m, sd = build(agent, data, head or "mlp", cuda=cuda, max_batch=max(64, n))
     m._ensure_bound()
@@ -103,6 +109,9 @@ def test_train_forward_backward_vs_oracle(cuda, agent, data, head, n, groups):
     rng = np.random.default_rng(n)
     x = rng.random((n, 3, hw, hw)).astype(np.float32)
     y = rng.integers(0, 10, n).astype(np.int64)
+    if images is not None:
+        x = np.ascontiguousarray(images, dtype=np.float32)
+        assert x.shape == (n, 3, hw, hw)
     xt = torch.from_numpy(x)
     per = n // groups
     # ---- engine forward

@@ -158,7 +158,11 @@ int ocl_clip_grad_norm(float* grads_inout, int64_t n, float max_norm, double* wo
  * torch.nn.CrossEntropyLoss(reduction='mean') (agents/base.py:95,113) and
  * F.cross_entropy(reduction='none') (utils/buffer/mir_retrieve.py:26-27).
  * reduction: 0 = none (loss_out[n]), 1 = mean (loss_out[1]).  dlogits (may be NULL) receives
- * d(loss)/d(logits) for reduction=mean, or d(loss_i)/d(logits_i) per row for reduction=none. */
+ * d(loss)/d(logits) for reduction=mean, or d(loss_i)/d(logits_i) per row for reduction=none.
+ * A label outside [0, c) (the reference raises) is never used as an address: that row's loss is NaN, so
+ * the mean is NaN; its dlogits row is written inside the row only (the softmax, no -1 anywhere); every
+ * other row's loss and dlogits have the bits of the same call with a valid label in that row's place.
+ * The same holds for the segmented form below (the row's softmax is then empty: its dlogits are 0). */
 int ocl_ce_fwd_bwd(const float* logits, const int64_t* y, int n, int c, int reduction,
                    float* loss_out, float* dlogits, void* stream);
 
@@ -251,7 +255,13 @@ int ocl_supcon_fwd_bwd(const float* feat, const int64_t* y, int bsz, int n_views
  * 94-116; distance = sum((u-v)^2), utils/utils.py:93-95).  One workgroup per evaluation row:
  * distances -> LDS bitonic sort (ties broken by ascending candidate index) -> label indicator ->
  * closed-form suffix recursion -> scatter to candidate order.  n_cand <= OCL_KNN_MAX_CAND.
- * sorted_idx (may be NULL) receives the per-row ascending-distance candidate order. */
+ * sorted_idx (may be NULL) receives the per-row ascending-distance candidate order.
+ * The per-row order is total: ascending distance, ties by ascending candidate index (+inf is an ordinary
+ * distance); then every candidate whose distance is NaN (a NaN in either row, or +inf in the same dimension
+ * of both), in index order; then, unseen by the caller, the sort's padding, which is known by its index and
+ * not by its key.  That is torch.argsort(distance, stable=True) on the CPU.  So for EVERY input sorted_idx[e]
+ * is a permutation of 0 .. n_cand - 1 and every cell of sv_out is written; the recursion reads labels and
+ * ranks only, so every value is finite whatever the features hold. */
 #define OCL_KNN_MAX_CAND 2048
 int ocl_knn_sv(const float* eval_f, const int64_t* eval_y, int n_eval, const float* cand_f,
                const int64_t* cand_y, int n_cand, int dim, int k, float* sv_out,
@@ -274,7 +284,8 @@ int ocl_argsort_desc(const float* v, int n, int64_t* idx_out, void* stream);
  * class, the mean re-normalised.  class_ids[n_cls] lists the labels in `old_labels` order; a class
  * with no exemplar gets count 0 and its mean row is left untouched (the caller fills it the way the
  * reference does, base.py:135-137).  predict returns argmin_j ||f/|f| - mean_j||^2 as an index
- * into class_ids (first minimum wins, like torch.min). */
+ * into class_ids (first minimum wins, like torch.min; a NaN distance counts as smaller than every
+ * number and the first NaN wins, as dists.min(1) has it on the CPU). */
 int ocl_ncm_class_means(const float* feat, const int64_t* labels, int n, int d,
                         const int64_t* class_ids, int n_cls, float* means_out, int32_t* counts_out,
                         void* stream);
@@ -282,7 +293,8 @@ int ocl_ncm_predict(const float* feat, int n, int d, const float* means, int n_c
                     int64_t* pred_out, void* stream);
 
 /* ---- K12: MIR interference score -------------------------------------------------------------------
- * post_loss - pre_loss with per-sample CE (utils/buffer/mir_retrieve.py:26-28). */
+ * post_loss - pre_loss with per-sample CE (utils/buffer/mir_retrieve.py:26-28).  A label outside
+ * [0, c) is never used as an address: that row's score is NaN, every other row's bits are unchanged (K6). */
 int ocl_mir_scores(const float* logits_pre, const float* logits_post, const int64_t* y, int n,
                    int c, float* scores_out, void* stream);
 
@@ -673,6 +685,11 @@ typedef struct {
     int64_t lds_bytes, lds2_bytes;     /* dynamic LDS of the two launches */
 } ocl_small_op_plan;
 int ocl_test_small_op_path(int op, const int64_t* args, int n_args, ocl_small_op_plan* plan);
+/* The sort of ocl_knn_sv (K10) replayed on the host, no GPU: n_cand (1 .. OCL_KNN_MAX_CAND) float keys are padded to the next
+ * power of two as the kernel pads them and sent through the kernel's network -- the same compare-exchange function, comparator
+ * and index arithmetic, one stage after the other -- and order_out receives the first n_cand indices.  For every input that is
+ * torch.argsort(keys, stable=True) (tests/test_cpu_small_ops.py). */
+int ocl_test_knn_order(const float* keys, int n_cand, int64_t* order_out);
 
 /* Run-to-run reproducibility.  The BatchNorm batch sums (forward statistics, backward reductions) are the only accumulations of a
  * step whose order depends on scheduling.  on = 1: they are accumulated as fixed-point integers (associative): every weight is

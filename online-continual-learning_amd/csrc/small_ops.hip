@@ -2,7 +2,9 @@
 // small MFMA GEMM.  HBM/latency-bound integer+fp32 work: coalesced 16-B accesses, LDS sorts, one
 // workgroup per row — none of this is reshaped into GEMMs.
 #include "flat_dev.h"
+#include <limits.h>
 #include <math.h>
+#include <vector>
 
 using namespace ocl;
 
@@ -280,12 +282,12 @@ __device__ __forceinline__ float ce_row(const float* __restrict__ x, int c, int6
     for (int j = lane; j < c; j += 64) s += expf(x[j] - m);
     s = wave_sum(s);
     const float lse = logf(s) + m;
-    const float xy = x[y];
+    const float xy = (uint64_t)y < (uint64_t)c ? x[y] : NAN;   // a label outside the row is no address: the row's loss is NaN (K6, K12)
     if (dx) {
         const float inv = 1.0f / s;
         for (int j = lane; j < c; j += 64) {
             float p = expf(x[j] - m) * inv;
-            dx[j] = (p - (j == (int)y ? 1.f : 0.f)) * scale;
+            dx[j] = (p - ((int64_t)j == y ? 1.f : 0.f)) * scale;
         }
     }
     if (exact) *exact = ((double)logf(s) + (double)m) - (double)xy;
@@ -317,7 +319,10 @@ __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logit
 // assigns every logit column to a segment (-1: takes no part); row r is a softmax over the columns of its label's segment.
 __device__ __forceinline__ float ce_row_seg(const float* __restrict__ x, const int* __restrict__ seg, int c, int64_t y, int lane,
                                             float* __restrict__ dx, float scale) {
-    const int sid = seg[y];
+    // a label outside the row is no address (K6): its segment id is one no column has (ids are >= -1), so the row's softmax is empty
+    // (dx = 0 in every column) and its loss NaN
+    const bool in_row = (uint64_t)y < (uint64_t)c;
+    const int sid = in_row ? seg[y] : INT_MIN;
     float m = -INFINITY;
     for (int j = lane; j < c; j += 64)
         if (seg[j] == sid) m = fmaxf(m, x[j]);
@@ -327,12 +332,12 @@ __device__ __forceinline__ float ce_row_seg(const float* __restrict__ x, const i
         if (seg[j] == sid) s += expf(x[j] - m);
     s = wave_sum(s);
     const float lse = logf(s) + m;
-    const float xy = x[y];
+    const float xy = in_row ? x[y] : NAN;
     if (dx) {
         const float inv = 1.0f / s;
         for (int j = lane; j < c; j += 64) {
             const float p = seg[j] == sid ? expf(x[j] - m) * inv : 0.f;
-            dx[j] = (p - (j == (int)y ? 1.f : 0.f)) * scale;
+            dx[j] = (p - ((int64_t)j == y ? 1.f : 0.f)) * scale;
         }
     }
     return lse - xy;
@@ -522,35 +527,61 @@ __global__ void __launch_bounds__(128) supcon_grad(const float* __restrict__ fea
 // =====================================================================================================
 // K10 kNN Shapley (utils/buffer/aser_utils.py:7-61,94-116)
 // =====================================================================================================
-__device__ __forceinline__ bool key_less(float ka, int ia, float kb, int ib) {
+// A bitonic network sorts only under a total order: with a comparator that answers "no" both ways for two different entries (every float
+// comparison against a NaN does) the network leaves an arbitrary arrangement, padding among the first n entries included.  Both orders
+// below are total over everything the arrays can hold; they are host functions too, so that ocl_test_knn_order replays the kernel's very
+// expressions on the CPU (tests/test_cpu_small_ops.py).
+__host__ __device__ __forceinline__ bool key_less(float ka, int ia, float kb, int ib) {
     return (ka < kb) || (ka == kb && ia < ib);
 }
 
-// the same order with NaN keys before every number (index order among themselves): argsort's NaN-first rule
-__device__ __forceinline__ bool key_less_nan_first(float ka, int ia, float kb, int ib) {
-    const bool na = isnan(ka), nb = isnan(kb);
+// kNN (K10): numbers ascending, ties by index (+inf is a number); then the NaN keys in index order; then the padding, known by its index
+// (idx >= n_real), never by its key -- a candidate at distance +inf ties with the padding's key and still sorts before it
+__host__ __device__ __forceinline__ bool key_less_nan_last(float ka, int ia, float kb, int ib, int n_real) {
+    // without a branch (every lane of the sort evaluates all of it).  Two numbers: the first line; a comparison against a NaN is false, so with
+    // a NaN the first line is false and the second decides: a < b if b is a NaN and a is a number or a NaN of lower index.  A real entry
+    // before the padding, and two padding entries are equal
+    const bool pa = ia >= n_real, pb = ib >= n_real, na = ka != ka, nb = kb != kb, il = ia < ib;
+    const bool num = (ka < kb) | ((ka == kb) & il);
+    const bool real = num | (nb & (!na | il));
+    return !pa & (pb | real);
+}
+
+// argsort: NaN keys before every number (index order among themselves), torch's descending NaN-first rule; the padding (+inf with the
+// largest index) is never a NaN and loses every tie, so it stays last
+__host__ __device__ __forceinline__ bool key_less_nan_first(float ka, int ia, float kb, int ib) {
+    const bool na = ka != ka, nb = kb != kb;
     if (na || nb) return na && (!nb || ia < ib);
     return key_less(ka, ia, kb, ib);
 }
 
-// in-LDS bitonic sort of P (pow2) (key, idx) pairs, ascending by (key, idx)
-template <bool NAN_FIRST = false>
-__device__ __forceinline__ void bitonic_sort_lds(float* key, int* idx, int P) {
+__host__ __device__ __forceinline__ void bitonic_pad(float* key, int* idx, int c) {
+    key[c] = INFINITY;
+    idx[c] = 0x7fffffff;
+}
+
+// compare-exchange number t (of P / 2) of the network's stage (k, j); the pairs of one stage are disjoint
+template <bool NAN_FIRST>
+__host__ __device__ __forceinline__ void bitonic_exchange(float* key, int* idx, int t, int j, int k, int n_real) {
+    const int lo = 2 * t - (t & (j - 1));      // j is a power of two: (t / j) * 2 j + t % j
+    const int hi = lo + j;
+    const bool up = ((lo & k) == 0);
+    const float ka = key[lo], kb = key[hi];
+    const int ia = idx[lo], ib = idx[hi];
+    const bool lt = NAN_FIRST ? key_less_nan_first(kb, ib, ka, ia) : key_less_nan_last(kb, ib, ka, ia, n_real);  // hi < lo
+    if (lt == up) {
+        key[lo] = kb; key[hi] = ka;
+        idx[lo] = ib; idx[hi] = ia;
+    }
+}
+
+// in-LDS bitonic sort of P (pow2) (key, idx) pairs, the first n_real real and the others padding, ascending in the order chosen
+template <bool NAN_FIRST>
+__device__ __forceinline__ void bitonic_sort_lds(float* key, int* idx, int P, int n_real) {
     for (int k = 2; k <= P; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
             __syncthreads();
-            for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
-                const int lo = ((t / j) * (j << 1)) + (t % j);
-                const int hi = lo + j;
-                const bool up = ((lo & k) == 0);
-                const float ka = key[lo], kb = key[hi];
-                const int ia = idx[lo], ib = idx[hi];
-                const bool lt = NAN_FIRST ? key_less_nan_first(kb, ib, ka, ia) : key_less(kb, ib, ka, ia);  // hi < lo
-                if (lt == up) {
-                    key[lo] = kb; key[hi] = ka;
-                    idx[lo] = ib; idx[hi] = ia;
-                }
-            }
+            for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) bitonic_exchange<NAN_FIRST>(key, idx, t, j, k, n_real);
         }
     }
     __syncthreads();
@@ -568,10 +599,7 @@ __global__ void __launch_bounds__(256) knn_sv_kernel(const float* __restrict__ e
     const int e = blockIdx.x;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
     for (int d = threadIdx.x; d < dim; d += blockDim.x) ef[d] = eval_f[(int64_t)e * dim + d];
-    for (int c = n_cand + threadIdx.x; c < P; c += blockDim.x) {
-        key[c] = INFINITY;
-        idx[c] = 0x7fffffff;
-    }
+    for (int c = n_cand + threadIdx.x; c < P; c += blockDim.x) bitonic_pad(key, idx, c);
     __syncthreads();
     // squared Euclidean distance sum((u-v)^2) (utils/utils.py:93-95): one THREAD per candidate, its feature row streamed with four
     // independent 16-byte loads in flight (rows are L2-resident: every workgroup reads the same candidates), the evaluation row
@@ -616,7 +644,7 @@ __global__ void __launch_bounds__(256) knn_sv_kernel(const float* __restrict__ e
             }
         }
     }
-    bitonic_sort_lds(key, idx, P);
+    bitonic_sort_lds<false>(key, idx, P, n_cand);   // a total order: idx[0 .. n_cand) is a permutation of the candidates for every input
     // indicator difference x factor (aser_utils.py:33-50), then reverse cumulative sum (:51-52)
     const int64_t ye = eval_y[e];
     const int N = n_cand;
@@ -733,11 +761,10 @@ __global__ void __launch_bounds__(256) argsort_desc_kernel(const float* __restri
             key[i] = -v[i];  // NaN stays NaN: first in torch's descending order, before +inf (key_less_nan_first)
             idx[i] = i;
         } else {
-            key[i] = INFINITY;
-            idx[i] = 0x7fffffff;
+            bitonic_pad(key, idx, i);
         }
     }
-    bitonic_sort_lds<true>(key, idx, P);
+    bitonic_sort_lds<true>(key, idx, P, n);
     for (int i = threadIdx.x; i < n; i += blockDim.x) out[i] = (int64_t)idx[i];
 }
 
@@ -807,7 +834,7 @@ __global__ void __launch_bounds__(256) ncm_predict_kernel(const float* __restric
         int best = 0;
         float bv = dist[0];
         for (int c = 1; c < n_cls; ++c)
-            if (dist[c] < bv) {
+            if (dist[c] < bv || (dist[c] != dist[c] && bv == bv)) {   // the first NaN wins and stays (torch.min), else the first minimum
                 bv = dist[c];
                 best = c;
             }
@@ -1330,6 +1357,23 @@ int ocl_test_small_op_path(int op, const int64_t* a, int na, ocl_small_op_plan* 
     }
     if (plan) *plan = p;
     return p.path;
+}
+
+int ocl_test_knn_order(const float* keys, int n_cand, int64_t* order_out) {
+    OCL_REQUIRE(keys && order_out && n_cand >= 1 && n_cand <= OCL_KNN_MAX_CAND, "knn_order: bad arguments");
+    const int P = next_pow2(n_cand);
+    std::vector<float> key(P);
+    std::vector<int> idx(P);
+    for (int c = 0; c < n_cand; ++c) {
+        key[c] = keys[c];
+        idx[c] = c;
+    }
+    for (int c = n_cand; c < P; ++c) bitonic_pad(key.data(), idx.data(), c);
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1)
+            for (int t = 0; t < (P >> 1); ++t) bitonic_exchange<false>(key.data(), idx.data(), t, j, k, n_cand);
+    for (int c = 0; c < n_cand; ++c) order_out[c] = (int64_t)idx[c];
+    return OCL_OK;
 }
 
 }  // extern "C"

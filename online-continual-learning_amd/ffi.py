@@ -167,6 +167,7 @@ SIGNATURES = {
     "ocl_test_head": (C.c_int, [C.POINTER(TestHeadArgs), vp]),
     "ocl_test_head_side_min_batch": (C.c_int, [C.c_int]),
     "ocl_test_small_op_path": (C.c_int, [C.c_int, C.POINTER(i64), C.c_int, C.POINTER(SmallOpPlan)]),
+    "ocl_test_knn_order": (C.c_int, [vp, C.c_int, vp]),
     "ocl_prof_enable": (C.c_int, [C.c_int]),
     "ocl_prof_reset": (C.c_int, []),
     "ocl_prof_query": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(i64)]),

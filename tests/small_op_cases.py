@@ -40,6 +40,11 @@ OPS = {
 EXEMPT_KERNELS = []
 
 
+def bad_labels(n, c):
+    """(row, label) of a bad_labels case: c, c + 5 and -1 in the first, a middle and the last row."""
+    return [(0, c), (n // 2, c + 5), (n - 1, -1)]
+
+
 def _c(name, key, path, seed, **kw):
     d = dict(name=name, key=key, path=path, seed=seed, off=0)
     d.update(kw)
@@ -99,14 +104,19 @@ COSINE = [
 # ---- cross-entropy family: n rows of c logits times `scale`; the last two rows are one dominant logit and all-equal logits ---------------
 _CE_SHAPES = [(1, 5, 1), (3, 10, 30), (4, 64, 1), (5, 100, 300), (10, 100, 1), (10, 128, 30), (37, 200, 1), (7, 1000, 300), (64, 63, 1)]
 CE = [_c("%s_n%d_c%d_s%d" % (red, n, c, s), "ce:%s n=%d c=%d scale=%d" % (red, n, c, s), "CE_" + red.upper(), 60 + i, n=n, c=c, scale=s, red=red)
-      for i, (n, c, s) in enumerate(_CE_SHAPES) for red in ("mean", "none")]
+      for i, (n, c, s) in enumerate(_CE_SHAPES) for red in ("mean", "none")] + \
+     [_c("%s_label_outside" % red, "ce:label_outside %s" % red, "CE_" + red.upper(), 70 + i, n=7, c=70, scale=1, red=red, bad_labels=True)
+      for i, red in enumerate(("mean", "none"))]
+# bad_labels: the labels of the first, a middle and the last row are c, c + 5 and -1 (bad_labels()): outside the row, inside the test's guard regions
 # seg: number of segments; a quarter of the columns (random positions) are -1
 CE_SEG = [_c("n%d_c%d_s%d_g%d" % (n, c, s, g), "ce_seg: n=%d c=%d scale=%d segments=%d" % (n, c, s, g), "CE_SEG", 80 + i, n=n, c=c, scale=s, seg=g)
-          for i, (n, c, s, g) in enumerate([(1, 5, 1, 1), (3, 10, 30, 2), (4, 64, 1, 2), (10, 100, 300, 3), (37, 200, 1, 2), (7, 1000, 30, 4), (10, 128, 1, 1)])]
+          for i, (n, c, s, g) in enumerate([(1, 5, 1, 1), (3, 10, 30, 2), (4, 64, 1, 2), (10, 100, 300, 3), (37, 200, 1, 2), (7, 1000, 30, 4), (10, 128, 1, 1)])] + \
+         [_c("label_outside", "ce_seg:label_outside", "CE_SEG", 88, n=7, c=70, scale=1, seg=2, bad_labels=True)]
 KD = [_c("n%d_c%d_s%d_T%g" % (n, c, s, T), "kd: n=%d c=%d scale=%d T=%g" % (n, c, s, T), "KD", 90 + i, n=n, c=c, scale=s, T=T)
       for i, (n, c, s, T) in enumerate([(1, 5, 1, 2.0), (3, 10, 30, 1.0), (4, 64, 1, 4.0), (10, 100, 300, 2.0), (37, 200, 1, 0.5), (7, 1000, 30, 3.0), (10, 128, 1, 2.0)])]
 MIR = [_c("n%d_c%d_s%d" % (n, c, s), "mir: n=%d c=%d scale=%d" % (n, c, s), "MIR", 100 + i, n=n, c=c, scale=s)
-       for i, (n, c, s) in enumerate([(1, 5, 1), (3, 10, 30), (4, 64, 1), (50, 100, 300), (37, 200, 1), (7, 1000, 30), (9, 128, 1)])]
+       for i, (n, c, s) in enumerate([(1, 5, 1), (3, 10, 30), (4, 64, 1), (50, 100, 300), (37, 200, 1), (7, 1000, 30), (9, 128, 1)])] + \
+      [_c("label_outside", "mir:label_outside", "MIR", 108, n=7, c=70, scale=1, bad_labels=True)]
 # ---- SupCon: view-major features [n_views * bsz, dim]; off: the feature pointer; want: full (gradient) or loss only ------------------
 SUPCON = [
     _c("A4_d4", "supcon/rows:vec A=4", "SUPCON_VEC_TAIL", 111, bsz=2, n_views=2, dim=4, T=0.07),
@@ -139,6 +149,20 @@ KNN = [
     _c("k_ge_n", "knn:k>=n_cand larger", "KNN_VEC_BOTH", 139, ne=3, nc=257, dim=20, k=300),
     _c("nc1", "knn:n_cand=1", "KNN_VEC_REM", 140, ne=2, nc=1, dim=4, k=3),
     _c("refuse", "knn:refuse_n_cand", "KNN_REFUSED", 141, ne=1, nc=2049, dim=8, k=3),
+    # special="nonfinite": integer-valued features with a NaN in one candidate row, +inf in another candidate (its key +inf ties with the
+    # padding's key), and per evaluation row: 0 plain, 1 +inf in that candidate's dimension (inf - inf: its key is NaN, every other +inf),
+    # 2 a NaN (every key NaN: the index order).  The keys are exact, +inf or NaN, so the order is fully determined (K10's total order)
+    _c("nf_d4_p4", "knn:nonfinite vec_rem n_cand=3 P=4", "KNN_VEC_REM", 142, ne=3, nc=3, dim=4, k=2, special="nonfinite"),
+    _c("nf_d6", "knn:nonfinite wave", "KNN_WAVE", 143, ne=3, nc=5, dim=6, k=3, special="nonfinite"),
+    _c("nf_d20", "knn:nonfinite vec_both", "KNN_VEC_BOTH", 144, ne=3, nc=9, dim=20, k=3, special="nonfinite"),
+    _c("nf_d16_p256", "knn:nonfinite vec_unroll n_cand=129 P=256", "KNN_VEC_UNROLL", 145, ne=3, nc=129, dim=16, k=7, special="nonfinite"),
+    _c("nf_d8_nopad", "knn:nonfinite no_padding n_cand=4", "KNN_VEC_REM", 146, ne=3, nc=4, dim=8, k=2, special="nonfinite"),
+    # data="real": the four distance paths on real-valued features (standard normal, clustered 100 + 1e-3 normal, near ties of one to four
+    # float32 ulps), judged against float64 by the derived bound of the path (tests/knn_ref.py); pairs: the near-tie pairs planted
+    _c("real_d12", "knn:real vec_rem", "KNN_VEC_REM", 147, ne=3, nc=37, dim=12, k=3, data="real", pairs=1),
+    _c("real_d70", "knn:real wave two trips", "KNN_WAVE", 148, ne=3, nc=50, dim=70, k=3, data="real", pairs=2),
+    _c("real_d36", "knn:real vec_both", "KNN_VEC_BOTH", 149, ne=3, nc=100, dim=36, k=5, data="real", pairs=4),
+    _c("real_d160", "knn:real vec_unroll aser shape", "KNN_VEC_UNROLL", 150, ne=3, nc=150, dim=160, k=3, data="real", pairs=6),
 ]
 COL_REDUCE = [_c("r%d_c%d" % (r, c), "col_reduce: rows=%d cols=%d" % (r, c), "COL_REDUCE", 150 + i, rows=r, cols=c)
               for i, (r, c) in enumerate([(97, 100), (3, 100), (8, 64), (16, 1), (64, 2048), (1, 33), (128, 96)])]
@@ -154,7 +178,10 @@ NCM_MEANS = [_c("n%d_d%d_c%d" % (n, d, c), "ncm_means: n=%d d=%d n_cls=%d absent
              for i, (n, d, c, a) in enumerate([(50, 160, 10, 0), (30, 640, 5, 1), (7, 100, 1, 0), (40, 300, 4, 2), (5, 7, 2, 0)])]
 NCM_PREDICT = [_c("n%d_d%d_c%d%s" % (n, d, c, "_ties" if t else ""), "ncm_predict: n=%d d=%d n_cls=%d ties=%d" % (n, d, c, t), "NCM_PREDICT", 200 + i,
                   n=n, d=d, n_cls=c, ties=t)
-               for i, (n, d, c, t) in enumerate([(50, 160, 10, 0), (30, 640, 100, 0), (7, 100, 1, 0), (40, 300, 7, 0), (20, 160, 10, 1), (9, 640, 6, 1), (0, 16, 3, 0)])]
+               for i, (n, d, c, t) in enumerate([(50, 160, 10, 0), (30, 640, 100, 0), (7, 100, 1, 0), (40, 300, 7, 0), (20, 160, 10, 1), (9, 640, 6, 1), (0, 16, 3, 0)])] + \
+              [_c("nan_" + w, "ncm_predict:nan " + what, "NCM_PREDICT", 207 + i, n=9, d=100, n_cls=6, ties=0, nan=w)
+               for i, (w, what) in enumerate([("mean", "one class mean (not class 0)"), ("feat", "one feature row: every distance"),
+                                              ("two_means", "two class means: the first wins")])]
 # ---- small GEMM: c[m, n] (+)= a b (+ bias) (relu).  at / bt: the operand is stored transposed.  The engine's forms (csrc/net.hip):
 # heads y = x W^T + b (bt, bias, relu 0 / 1); dW (+)= dy^T x (at, accumulate 0 / 1); dx = dy W (neither).  pad: c_rs - n ----------------
 _G_K = [16, 17, 19, 4, 15, 640, 1, 160]        # k % 16 in {0, 1..3, 4, 15}, the feature widths 160 / 640
@@ -218,7 +245,10 @@ REQUIRED_KEYS = [
     "knn:vec_both d4n=6", "knn:vec_both d4n=7", "knn:wave misaligned", "knn:k>=n_cand larger", "ncm_means: n=30 d=640", "ncm_predict: n=20 d=160 n_cls=10 ties=1",
     "col_reduce: rows=3 ", "col_reduce: rows=8 cols=64", "col_reduce: rows=16 cols=1", "col_reduce: rows=64 cols=2048", "argsort: n=2 zeros", "argsort: n=3 inf",
     "argsort: n=64 nan", "augment:orders", "augment:hsv_sectors", "augment:partial_block", "augment:fractional_crop", "augment:clamps", "augment:gray",
-    "augment:misaligned", "augment:guard", "augment:refuse", "aug_params:partial_block", "aug_params:extremes",
+    "knn:nonfinite vec_rem n_cand=3 P=4", "knn:nonfinite wave", "knn:nonfinite vec_both", "knn:nonfinite vec_unroll n_cand=129 P=256",
+    "knn:nonfinite no_padding", "knn:real vec_rem", "knn:real wave", "knn:real vec_both", "knn:real vec_unroll", "ce:label_outside mean",
+    "ce:label_outside none", "ce_seg:label_outside", "mir:label_outside", "ncm_predict:nan one class mean", "ncm_predict:nan one feature row",
+    "ncm_predict:nan two class means", "augment:misaligned", "augment:guard", "augment:refuse", "aug_params:partial_block", "aug_params:extremes",
 ]
 
 

@@ -121,8 +121,8 @@ def test_plans_are_what_the_header_documents(lib):
 
 
 # the size of the table: a case that leaves it (or joins it) is a deliberate edit of this line too
-CASE_COUNTS = {"rows": 9, "pair": 7, "u8": 5, "sgd": 8, "cosine": 13, "ce": 18, "ce_seg": 7, "kd": 7, "mir": 7, "supcon": 16, "knn": 11,
-               "col_reduce": 7, "aser": 6, "argsort": 12, "ncm_means": 5, "ncm_predict": 7, "gemm": 56, "augment": 16, "aug_params": 17}
+CASE_COUNTS = {"rows": 9, "pair": 7, "u8": 5, "sgd": 8, "cosine": 13, "ce": 20, "ce_seg": 8, "kd": 7, "mir": 8, "supcon": 16, "knn": 20,
+               "col_reduce": 7, "aser": 6, "argsort": 12, "ncm_means": 5, "ncm_predict": 10, "gemm": 56, "augment": 16, "aug_params": 17}
 
 
 def test_no_case_left_the_table():
@@ -403,3 +403,124 @@ def test_aug_params_reference_and_its_exclusions(name):
     if c.get("special") == "extremes":
         assert (u[0] == 0).all() and (u[1] == np.float32(1 - U)).all() and (u[2, 20:] == 0).all() and (u[3, 20:] == np.float32(1 - U)).all()
         assert ok[0] and ok[2] and P[0, 10] == 0 and P[3, 10] == 23 and P[2, 0] == 0 and P[3, 0] + P[3, 2] == c["h"]
+
+
+# ---- kNN-Shapley: the sort's total order replayed on the host, and the conditions of the non-finite and the real-valued cases ----------------
+def _replay(lib, keys):
+    """ocl_test_knn_order on every row of keys [m, n]: the kernel's padding, network and comparator, run on the host."""
+    keys = np.ascontiguousarray(keys, dtype=np.float32)
+    m, n = keys.shape
+    out = np.full((m, n), -1, dtype=np.int64)
+    pk, po = keys.ctypes.data, out.ctypes.data
+    for i in range(m):
+        assert lib.ocl_test_knn_order(pk + 4 * n * i, n, po + 8 * n * i) == 0
+    return out
+
+
+def _torch_stable(keys):
+    import torch
+    return torch.argsort(torch.from_numpy(np.ascontiguousarray(keys, dtype=np.float32)), dim=1, stable=True).numpy()
+
+
+def _assert_order(lib, keys, what):
+    got, exp = _replay(lib, keys), _torch_stable(keys)
+    bad = np.nonzero((got != exp).any(1))[0]
+    assert bad.size == 0, "%s: %d of %d vectors are not in the stable order; first: keys %s give %s, not %s" % (
+        what, bad.size, len(keys), keys[bad[0]].tolist(), got[bad[0]].tolist(), exp[bad[0]].tolist())
+
+
+def test_knn_order_replay_is_the_stable_argsort_exhaustively(lib):
+    """Every key vector of length 1 to 8 over {0, 1, +inf, -inf, NaN} (488280 vectors; lengths 3, 5, 6, 7 are padded, with +inf keys that tie
+    with the padding's): the kernel's network with its comparator returns torch.argsort(keys, stable=True) -- numbers ascending with ties by
+    index, then the NaNs by index, the padding never among the first n.  (With the earlier comparator, under which NaN compares false both ways,
+    the smallest failure was n = 3: [0.0027, 0.857, NaN] -> [0, 1, 2147483647].)"""
+    alphabet = np.array([0.0, 1.0, np.inf, -np.inf, np.nan], dtype=np.float32)
+    for n in range(1, 9):
+        digits = (np.arange(5 ** n)[:, None] // 5 ** np.arange(n)[None, :]) % 5
+        _assert_order(lib, alphabet[digits], "alphabet vectors of length %d" % n)
+
+
+@pytest.mark.parametrize("n", [3, 5, 33, 100, 150, 257, 2047, 2048])
+def test_knn_order_replay_on_random_keys(lib, n):
+    """Seeded random keys (distinct normals, or few distinct values: ties; some with +-inf) with no NaN, one NaN, many NaNs (up to a third, and
+    all but one) and the all-NaN vector, at the sizes ASER draws (100, 150), just past a power of two, and at and just under the cap."""
+    rng = np.random.default_rng(1000 + n)
+    rows = []
+    for rep in range(24 if n <= 257 else 6):
+        v = rng.standard_normal(n).astype(np.float32) ** 2
+        if rep % 3 == 1:
+            v = rng.integers(0, 4, n).astype(np.float32)
+        if rep % 3 == 2:
+            v[rng.integers(0, n, max(1, n // 8))] = np.inf
+            v[rng.integers(0, n, max(1, n // 16))] = -np.inf
+        for nans in (0, 1, max(2, n // 3), n - 1, n):
+            w = v.copy()
+            w[rng.permutation(n)[:nans]] = np.nan
+            assert int(np.isnan(w).sum()) == min(nans, n)
+            rows.append(w)
+    _assert_order(lib, np.stack(rows), "random keys, n = %d" % n)
+
+
+def test_knn_order_replay_refuses_a_wrong_call(lib):
+    k = np.zeros(4, dtype=np.float32)
+    o = np.zeros(4, dtype=np.int64)
+    assert lib.ocl_test_knn_order(k.ctypes.data, 0, o.ctypes.data) != 0
+    assert lib.ocl_test_knn_order(k.ctypes.data, 2049, o.ctypes.data) != 0
+    assert lib.ocl_test_knn_order(None, 4, o.ctypes.data) != 0 and lib.ocl_test_knn_order(k.ctypes.data, 4, None) != 0
+
+
+def _knn_cases(**kw):
+    return [c for c in SC.CASES["knn"] if all(c.get(k) == v for k, v in kw.items())]
+
+
+def test_knn_nonfinite_cases_have_a_determined_order(lib):
+    """The five non-finite cases: every key is an exact integer, +inf or NaN; row 0 has a NaN key and a +inf key among finite ones, row 1 only
+    +inf and NaN keys, row 2 only NaN keys; and the host replay of the kernel's sort puts the float32 keys in the stable order the GPU test
+    expects of the kernel (this runs before any of these cases is sent to a device)."""
+    import knn_ref as KR
+    cases = _knn_cases(special="nonfinite")
+    assert sorted((c["nc"], c["dim"], c["path"]) for c in cases) == [(3, 4, "KNN_VEC_REM"), (4, 8, "KNN_VEC_REM"), (5, 6, "KNN_WAVE"),
+                                                                       (9, 20, "KNN_VEC_BOTH"), (129, 16, "KNN_VEC_UNROLL")]
+    for c in cases:
+        ef, ey, cf, cy = KR.nonfinite_inputs(c)
+        d = KR.keys64(ef, cf)
+        fin = np.isfinite(d)
+        assert (d[fin] == np.floor(d[fin])).all() and d[fin].max() < 2 ** 24
+        n_nan = 1 if c["nc"] < 9 else 2
+        assert np.isnan(d[0]).sum() == n_nan and np.isinf(d[0]).sum() == n_nan and fin[0].sum() == c["nc"] - 2 * n_nan
+        assert np.isnan(d[1]).sum() == 2 * n_nan and np.isinf(d[1]).sum() == c["nc"] - 2 * n_nan
+        assert np.isnan(d[2]).all()
+        order = KR.stable_order(d)
+        assert np.array_equal(order[2], np.arange(c["nc"]))
+        for r in range(3):      # K10 in words: numbers ascending (+inf one of them), then the NaNs; ties by index
+            assert order[r].tolist() == sorted(range(c["nc"]), key=lambda j: (bool(np.isnan(d[r, j])), 0.0 if np.isnan(d[r, j]) else d[r, j], j))
+        with np.errstate(invalid="ignore", over="ignore"):
+            k32 = d.astype(np.float32)
+        assert np.array_equal(_replay(lib, k32), order), c["name"]
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in SC.CASES["knn"] if c.get("data") == "real"])
+def test_knn_real_cases_test_the_order_and_not_the_tolerance(name):
+    """Per kind of data, from the reference alone: a float32 restatement of the case's distance path, in the kernel's order of operations, gives
+    an order whose adjacent pairs float64 orders the other way are all inside 1.01 K 2^-24 (d_a + d_b) (knn_ref.path_k: the bound is what the
+    arithmetic costs), and they are at most 5 % of the adjacent pairs (else the case would test the tolerance); the planted near ties are one
+    to four float32 ulps apart and the clustered data is as ill-conditioned as it claims."""
+    import knn_ref as KR
+    c = [c for c in SC.CASES["knn"] if c["name"] == name][0]
+    K = KR.path_k(c["path"], c["dim"])
+    assert K == {"real_d12": 7, "real_d70": 10, "real_d36": 13, "real_d160": 44}[name]
+    for kind in KR.KINDS:
+        ef, ey, cf, cy = KR.real_inputs(c, kind)
+        assert ef.dtype == cf.dtype == np.float32 and ef.shape == (c["ne"], c["dim"]) and cf.shape == (c["nc"], c["dim"])
+        d64 = KR.keys64(ef, cf)
+        k32 = KR.restate32(c["path"], ef, cf)
+        assert k32.dtype == np.float32 and np.abs(k32 - d64).max() <= (1.01 * K * U * d64).max()
+        n_inv, n_pairs, gap, bound = KR.inverted_pairs(np.argsort(k32, axis=1, kind="stable"), d64, K)
+        print("%s/%s: K = %d, %d of %d adjacent pairs inverted, worst gap %.3g against %.3g" % (name, kind, K, n_inv, n_pairs, gap, bound))
+        assert gap <= bound, (name, kind, gap, bound)
+        assert n_inv <= 0.05 * n_pairs, (name, kind, n_inv, n_pairs)
+        if kind == "near_tie":
+            ulps = KR.near_tie_ulps(c, ef, cf)
+            assert len(ulps) == c["pairs"] >= 1 and all(1.0 <= u <= 4.0 for u in ulps), ulps
+        if kind == "clustered":
+            assert d64.max() < 1e-4 * c["dim"] and (ef.astype(np.float64) ** 2).sum(1).min() > 9e3 * c["dim"]

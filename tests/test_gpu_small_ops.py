@@ -2,9 +2,12 @@
 written here (the augmentation's: tests/augment_ref.py) from the formulas include/ocl_hip.h cites -- independent of oracle/ (fp32) and of the library.
 
 Tier 1 (bit-equal, data chosen so that fp32 is exact): gather / scatter / pair / u8 (any data), the small GEMM and the column reductions on small
-integers, SGD with power-of-two hyper-parameters, argsort order, kNN order and Shapley values on integer-valued features, NCM ties.
+integers, SGD with power-of-two hyper-parameters, argsort order, kNN order and Shapley values on integer-valued features (with NaN and +inf
+planted among them: include/ocl_hip.h K10's total order), NCM ties and NaN distances, labels outside the row in ce / ce_seg / mir (K6, K12).
 Tier 2 (random fp32, per-element error against float64):
   * sums of products: |got - ref| <= 1.01 * K * 2^-24 * sum|terms|, K the number of fp32-accumulated terms (derived, no measured number);
+  * the kNN order on real-valued features: an adjacent pair that float64 orders the other way is within 1.01 * K * 2^-24 * (d_a + d_b), K the
+    roundings of the case's distance path (tests/knn_ref.py); the Shapley values are bit-equal to the oracle's for the kernel's order;
   * transcendental kernels (ce, ce_seg, kd, mir, supcon): the same formula evaluated by plain torch-CPU fp32 on the same inputs has error e_ref
     against float64 (max over the tensor); the kernel's must be <= max(4 * e_ref, 4 ulp of the largest |reference| element).  4: the kernel and
     torch differ in summation order and in expf / logf (each ~2 ulp per term), nothing else; a wrong factor, a dropped term or a wrong max is orders
@@ -23,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 import augment_ref as AR
+import knn_ref as KR
 import parity_bounds as PB
 import small_op_cases as SC
 from guarded import Guarded
@@ -509,11 +513,66 @@ def test_argsort_desc_order(lib, name):
 # ==========================================================================================================================================
 # kNN-Shapley
 # ==========================================================================================================================================
+def _knn_call(lib, c, ef, ey, cf, cy, what):
+    """One ocl_knn_sv call on guarded tensors, on the path the case names: (sorted_idx, sv_out) as numpy.  Guards intact, inputs unchanged, every
+    row of sorted_idx a permutation of the candidates, no cell of sv_out left unwritten, every value finite."""
+    ne, nc, dim, k = c["ne"], c["nc"], c["dim"], c["k"]
+    g = Guarded()
+    d_ef, d_ey, d_cf, d_cy = g.inp(ef, 0, "eval_f"), g.inp(ey, 0, "eval_y"), g.inp(cf, c["off"], "cand_f"), g.inp(cy, 0, "cand_y")
+    d_sv, d_ord = g.out((ne, nc), torch.float32, 0, "sv"), g.out((ne, nc), torch.int64, 0, "order")
+    assert_path(lib, "knn", c, [d_cf])
+    ok(lib, lib.ocl_knn_sv(vp(d_ef), vp(d_ey), ne, vp(d_cf), vp(d_cy), nc, dim, k, vp(d_sv), vp(d_ord), stream()), what)
+    g.check(what)
+    order, sv = d_ord.cpu().numpy(), d_sv.cpu().numpy()
+    assert np.array_equal(np.sort(order, axis=1), np.tile(np.arange(nc), (ne, 1))), "%s: a row of sorted_idx is no permutation" % what
+    assert not (sv == Guarded.POISON).any(), "%s: %d cells of sv_out were not written" % (what, int((sv == Guarded.POISON).sum()))
+    assert np.isfinite(sv).all(), what
+    return order, sv
+
+
+def _knn_nonfinite_case(lib, c):
+    """special="nonfinite" (knn_ref.nonfinite_inputs): NaN and +inf among integer-valued features.  Every key is exact, +inf or NaN, so K10's
+    total order -- torch.argsort(keys, stable=True) -- is fully determined: sorted_idx must be that order, sv_out the oracle's bits for it."""
+    from oracle import ocl_oracle as O
+    ef, ey, cf, cy = KR.nonfinite_inputs(c)
+    exp_order = KR.stable_order(KR.keys64(ef, cf))
+    order, sv = _knn_call(lib, c, ef, ey, cf, cy, c["name"])
+    for r in range(c["ne"]):
+        assert np.array_equal(order[r], exp_order[r]), "%s row %d: %s, not %s" % (c["name"], r, order[r].tolist(), exp_order[r].tolist())
+    exp, _ = O.knn_sv(ef, ey, cf, cy, c["k"], order=exp_order)
+    assert sv.tobytes() == exp.tobytes(), "%s: max diff %g" % (c["name"], np.abs(sv - exp).max())
+
+
+def _knn_real_case(lib, c):
+    """data="real" (knn_ref.real_inputs: standard normal, clustered, near ties): the kernel's order must be an ascending order of the float64
+    distances up to the path's rounding -- every adjacent pair that float64 orders the other way is within 1.01 K 2^-24 (d_a + d_b), K =
+    knn_ref.path_k (derived there from the kernel's code: 2 for the subtraction under the square, the fused steps of the longest lane chain,
+    the final adds or the shuffle tree) -- and, given that order, sv_out has the oracle's bits."""
+    from oracle import ocl_oracle as O
+    K = KR.path_k(c["path"], c["dim"])
+    for kind in KR.KINDS:
+        what = "knn/%s/%s" % (c["name"], kind)
+        ef, ey, cf, cy = KR.real_inputs(c, kind)
+        order, sv = _knn_call(lib, c, ef, ey, cf, cy, what)
+        n_inv, n_pairs, gap, bound = KR.inverted_pairs(order, KR.keys64(ef, cf), K)
+        PB.record(REPORT, what, "order", gap, None, bound)
+        print("%s: K = %d, %d of %d adjacent pairs inverted against float64, worst gap %.4g, bound %.4g" % (what, K, n_inv, n_pairs, gap, bound))
+        assert gap <= bound, "%s: the order is not ascending in float64 beyond round-off: gap %.4g, bound %.4g" % (what, gap, bound)
+        exp, _ = O.knn_sv(ef, ey, cf, cy, c["k"], order=order)
+        assert sv.tobytes() == exp.tobytes(), "%s: max diff %g" % (what, np.abs(sv - exp).max())
+
+
 @case_of("knn")
 def test_knn_sv_on_integer_features(lib, name):
-    """Integer-valued features: squared distances are exact in fp32, so the order -- index-ordered ties included -- is fully determined."""
+    """Integer-valued features: squared distances are exact in fp32, so the order -- index-ordered ties included -- is fully determined; with
+    NaN and +inf planted among them (special="nonfinite") it still is.  The cases on real-valued features (data="real") are judged by the
+    derived bound of their distance path (_knn_real_case)."""
     from oracle import ocl_oracle as O
     c = find("knn", name)
+    if c.get("special") == "nonfinite":
+        return _knn_nonfinite_case(lib, c)
+    if c.get("data") == "real":
+        return _knn_real_case(lib, c)
     rng = np.random.default_rng(c["seed"])
     ne, nc, dim, k = c["ne"], c["nc"], c["dim"], c["k"]
     ef = rng.integers(-4, 5, (ne, dim)).astype(np.float32)
@@ -546,6 +605,22 @@ def test_knn_sv_on_integer_features(lib, name):
         for r in range(ne):
             bf = shapley_subsets(d64[r], cy == ey[r], k)
             assert np.abs(got[r].astype(np.float64) - bf).max() <= nc * 2.0 ** -23, (name, r)
+
+
+def test_knn_sv_op_orders_nonfinite_features(cuda):
+    """ops.knn_sv(want_order=True), the call the ASER plugins make, on the non-finite cases' data: every row of the order is a permutation of
+    the candidates -- the stable order of the keys -- and the values are the oracle's for it (the op allocates sv_out uninitialised)."""
+    from ocl_amd import ops
+    from oracle import ocl_oracle as O
+    for c in [c for c in SC.CASES["knn"] if c.get("special") == "nonfinite"]:
+        ef, ey, cf, cy = KR.nonfinite_inputs(c)
+        sv, order = ops.knn_sv(*(torch.from_numpy(a).cuda() for a in (ef, ey, cf, cy)), c["k"], want_order=True)
+        order, sv = order.cpu().numpy(), sv.cpu().numpy()
+        for r in range(c["ne"]):
+            assert sorted(order[r].tolist()) == list(range(c["nc"])), (c["name"], r, order[r].tolist())
+        exp_order = KR.stable_order(KR.keys64(ef, cf))
+        assert np.array_equal(order, exp_order), c["name"]
+        assert sv.tobytes() == O.knn_sv(ef, ey, cf, cy, c["k"], order=exp_order)[0].tobytes(), c["name"]
 
 
 # ==========================================================================================================================================
@@ -610,6 +685,14 @@ def test_ncm_predict(lib, name):
         for j in range(0, ncls - 1, 2):
             means[j + 1] = means[j]
         feat = (means[rng.integers(0, ncls, n)] * np.float32(3.0) + rng.standard_normal((n, d)).astype(np.float32) * np.float32(0.01)).astype(np.float32)
+    if c.get("nan"):
+        # NaN distances (K11): torch.min's rule on the CPU, the first NaN wins and otherwise the first minimum.  Rows near one mean each, so
+        # that the rows without a NaN are decided far outside round-off
+        feat = (means[rng.integers(0, ncls, n)] * np.float32(3.0) + rng.standard_normal((n, d)).astype(np.float32) * np.float32(0.01)).astype(np.float32)
+        if c["nan"] == "feat":
+            feat[n // 2, d - 1] = np.nan
+        for cls in {"mean": [3], "two_means": [4, 2], "feat": []}[c["nan"]]:
+            means[cls, cls] = np.nan
     g = Guarded()
     d_f = g.inp(feat if n else np.zeros((1, d), dtype=np.float32), 0, "feat")
     d_m, d_p = g.inp(means, 0, "means"), g.out((max(n, 1),), torch.int64, 0, "pred")
@@ -624,6 +707,13 @@ def test_ncm_predict(lib, name):
     fn = f64 / np.linalg.norm(f64, axis=1, keepdims=True)
     t = fn[:, None, :] - means.astype(np.float64)[None, :, :]
     d64 = (t ** 2).sum(-1)
+    if c.get("nan"):
+        exp = torch.min(torch.from_numpy(d64), 1).indices.numpy()
+        nan_rows = np.isnan(d64).any(1)
+        assert nan_rows.sum() == (1 if c["nan"] == "feat" else n) and (exp[nan_rows] == {"mean": 3, "two_means": 2, "feat": 0}[c["nan"]]).all()
+        assert np.array_equal(exp[~nan_rows], d64[~nan_rows].argmin(1))
+        assert np.array_equal(pred, exp), "%s: %s, torch.min gives %s" % (name, pred.tolist(), exp.tolist())
+        return
     bound = 1.01 * (math.ceil(d / 64.0) + 6) * U * d64 + 2 * 1.01 * (_norm_k(d) + 1) * U * (np.abs(t) * np.abs(fn)[:, None, :]).sum(-1)
     assert ((pred >= 0) & (pred < ncls)).all()
     best = d64.argmin(1)
@@ -700,11 +790,80 @@ def _cap(c):
     return 1e-5 if c["scale"] == 1 and (c["n"], c["c"]) == (10, 100) else None
 
 
+def _labels_outside_case(lib, op, c):
+    """bad_labels cases of ce, ce_seg and mir (K6, K12): the labels c, c + 5 and -1 in the first, a middle and the last row.  Every tensor is
+    guarded, so label-addressed reads with these offsets would stay inside the test's own allocation (and return a sentinel or a neighbour's
+    logit: a finite, wrong loss).  The contract: a bad row's loss (and so the mean, and the MIR score) is NaN; every other row's loss and
+    dlogits have the bits of the same call with valid labels in the bad rows; a bad row's dlogits stay inside the row -- the softmax alone
+    (ce: the valid call's row except at that call's label) or, segmented, zeros."""
+    rng = np.random.default_rng(c["seed"])
+    n, cc = c["n"], c["c"]
+    bad = SC.bad_labels(n, cc)
+    bad_rows = [r for r, _ in bad]
+    assert len(set(bad_rows)) == 3 and bad_rows[0] == 0 and bad_rows[2] == n - 1 and [v for _, v in bad] == [cc, cc + 5, -1]
+    x, x2 = logits_for(rng, n, cc, c["scale"]), logits_for(rng, n, cc, c["scale"])
+    seg = rng.integers(0, c.get("seg", 1), cc).astype(np.int32)
+    seg[rng.permutation(cc)[: cc // 4]] = -1
+    live = np.nonzero(seg >= 0)[0]
+    y_ok = live[rng.integers(0, len(live), n)].astype(np.int64)
+    y_bad = y_ok.copy()
+    for r, v in bad:
+        y_bad[r] = v
+    good_rows = np.array([r for r in range(n) if r not in bad_rows])
+
+    def run(y, tag):
+        g = Guarded()
+        d_x, d_y = g.inp(x, 0, "logits"), g.inp(y, 0, "y")
+        if op == "mir":
+            d_x2, d_o = g.inp(x2, 0, "post"), g.out((n,), torch.float32, 0, "scores")
+            assert_path(lib, "mir", c)
+            ok(lib, lib.ocl_mir_scores(vp(d_x), vp(d_x2), vp(d_y), n, cc, vp(d_o), stream()), tag)
+            g.check(tag)
+            return d_o.cpu().numpy(), None
+        d_dx = g.out((n, cc), torch.float32, 0, "dlogits")
+        assert_path(lib, op, c)
+        if op == "ce":
+            red = 1 if c["red"] == "mean" else 0
+            d_l, d_l2 = g.out((1 if red else n,), torch.float32, 0, "loss"), g.out((1 if red else n,), torch.float32, 0, "loss2")
+            ok(lib, lib.ocl_ce_fwd_bwd(vp(d_x), vp(d_y), n, cc, red, vp(d_l), vp(d_dx), stream()), tag)
+            ok(lib, lib.ocl_ce_fwd_bwd(vp(d_x), vp(d_y), n, cc, red, vp(d_l2), None, stream()), tag)
+        else:
+            d_s = g.inp(seg, 0, "seg")
+            d_l, d_l2 = g.out((1,), torch.float32, 0, "loss"), g.out((1,), torch.float32, 0, "loss2")
+            ok(lib, lib.ocl_ce_segmented_fwd_bwd(vp(d_x), vp(d_y), vp(d_s), n, cc, vp(d_l), vp(d_dx), stream()), tag)
+            ok(lib, lib.ocl_ce_segmented_fwd_bwd(vp(d_x), vp(d_y), vp(d_s), n, cc, vp(d_l2), None, stream()), tag)
+        g.check(tag)
+        assert d_l.cpu().numpy().tobytes() == d_l2.cpu().numpy().tobytes()
+        return d_l.cpu().numpy(), d_dx.cpu().numpy()
+
+    l_ok, dx_ok = run(y_ok, c["name"] + " (valid labels)")
+    l_bad, dx_bad = run(y_bad, c["name"])
+    assert np.isfinite(l_ok).all()
+    if len(l_bad) == n:                                             # per-row losses / scores
+        assert np.isnan(l_bad[bad_rows]).all(), "%s: rows %s: %s" % (c["name"], bad_rows, l_bad[bad_rows].tolist())
+        assert l_bad[good_rows].tobytes() == l_ok[good_rows].tobytes()
+    else:
+        assert np.isnan(l_bad).all(), "%s: the mean is %r" % (c["name"], l_bad.tolist())
+    if dx_bad is None:
+        return
+    assert not (dx_bad == Guarded.POISON).any()
+    assert dx_bad[good_rows].tobytes() == dx_ok[good_rows].tobytes(), "%s: the gradient of a row with a valid label changed" % c["name"]
+    for r in bad_rows:
+        if op == "ce":
+            keep = np.arange(cc) != y_ok[r]
+            assert dx_bad[r][keep].tobytes() == dx_ok[r][keep].tobytes() and np.isfinite(dx_bad[r]).all(), (c["name"], r)
+            assert dx_bad[r, y_ok[r]] > dx_ok[r, y_ok[r]]          # the softmax, without the valid call's -1 at its label
+        else:
+            assert (dx_bad[r] == 0).all(), (c["name"], r)
+
+
 @case_of("ce")
 def test_cross_entropy(lib, name):
     """Loss and gradient in one call, loss only (dlogits NULL: bit-equal loss), reduction none and mean; the gradient target is a row block
     in the middle of a larger buffer (guarded on both sides like every tensor here)."""
     c = find("ce", name)
+    if c.get("bad_labels"):
+        return _labels_outside_case(lib, "ce", c)
     rng = np.random.default_rng(c["seed"])
     n, cc = c["n"], c["c"]
     x = logits_for(rng, n, cc, c["scale"])
@@ -729,6 +888,8 @@ def test_cross_entropy(lib, name):
 @case_of("ce_seg")
 def test_cross_entropy_segmented(lib, name):
     c = find("ce_seg", name)
+    if c.get("bad_labels"):
+        return _labels_outside_case(lib, "ce_seg", c)
     rng = np.random.default_rng(c["seed"])
     n, cc = c["n"], c["c"]
     x = logits_for(rng, n, cc, c["scale"])
@@ -785,6 +946,8 @@ def test_mir_scores(lib, name):
     element); mir_kernel now combines the pieces of both losses in double (1.209e-07 on the same case)."""
     from oracle import ocl_oracle as O
     c = find("mir", name)
+    if c.get("bad_labels"):
+        return _labels_outside_case(lib, "mir", c)
     rng = np.random.default_rng(c["seed"])
     n, cc = c["n"], c["c"]
     pre, post = logits_for(rng, n, cc, c["scale"]), logits_for(rng, n, cc, c["scale"])

@@ -4,6 +4,7 @@
 // (OCL_WGRAD_Q, OCL_BNB_EPI, OCL_GRAPH, OCL_DETERMINISTIC, ...) through the whole pass, tensor by tensor:
 //   netcheck <n> <groups> <hw> <head> write  ref.bin
 //   OCL_WGRAD_Q=1 netcheck <n> <groups> <hw> <head> compare ref.bin      -> per-tensor max |a - b| / max |b|, exit 1 above 1e-4
+//   NETCHECK_WS_FILL=ff netcheck ... compare ref.bin   (ref.bin written with NETCHECK_WS_FILL=00) -> nothing may depend on what the workspace held
 // It is a measurement / validation tool like kbench; the product path is the Python host side.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -91,6 +92,16 @@ int main(int argc, char** argv) {
     CK(hipMemset(nbt, 0, nbn * 8));
     CK(hipMemcpy(x, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(dout, hd.data(), hd.size() * 4, hipMemcpyHostToDevice));
+    // NETCHECK_WS_FILL=<two hex digits>: every workspace byte holds that value before the bind (ff: NaN as a float, UINT_MAX as a counter);
+    // unset, the workspace is what hipMalloc returned.  No result may depend on it (tests/test_gpu_ws_poison.py).
+    if (const char* fill = getenv("NETCHECK_WS_FILL")) {
+        char* end = nullptr;
+        const long v = strtol(fill, &end, 16);
+        if (strlen(fill) != 2 || *end || v < 0 || v > 255) { fprintf(stderr, "NETCHECK_WS_FILL: two hex digits, got '%s'\n", fill); return 2; }
+        CK(hipMemset(ws, (int)v, wsb));
+        CK(hipDeviceSynchronize());
+        printf("netcheck: workspace of %lld bytes filled with 0x%02lx\n", (long long)wsb, v);
+    }
     OK(ocl_net_bind(net, p, g, r, nbt, ws, wsb));
     hipStream_t s;
     CK(hipStreamCreate(&s));

@@ -6,6 +6,8 @@ with one, tensor by tensor.  The planner reads its knobs once per process, so th
 
   * the 4x4x1 form of layer 1 (the default where the planner's gate takes it; OCL_WGRAD_Q=0 = the 16x16x4 form everywhere) sums in another
     order: exactly the four 3x3 weights of layer 1 may differ, by rounding; on the passes the gate leaves alone nothing may differ.
+  * NETCHECK_WS_FILL: the workspace holds 0x00 or 0xff in every byte before the bind; in every run-time mode of ws_poison_cases.NETCHECK_MODES
+    not one bit may depend on it (the law of tests/test_gpu_ws_poison.py, through the C ABI).
 """
 import os
 import re
@@ -114,3 +116,25 @@ def test_channel_partitioned_batchnorm_backward_differs_by_rounding_only(cfg, tm
     rc, out2 = _run(cfg, "compare", ref, {"OCL_BN_CHAN": "0"})     # the switch is read: the same mode again is bit-identical
     m = re.search(r"(\d+) of (\d+) tensors differ in some bit", out2)
     assert rc == 0 and m and int(m.group(1)) == 0, out2
+
+
+def _poison_matrix():
+    import ws_poison_cases as WC
+    rows = [(mode, cfg) for mode in WC.NETCHECK_MODES for cfg in WC.NETCHECK_CASES]
+    return rows + [({}, cfg) for cfg in WC.NETCHECK_DEFAULT_ONLY]
+
+
+@pytest.mark.parametrize("mode,cfg", _poison_matrix(),
+                         ids=lambda v: "n%d_g%d_hw%d_head%d" % v if isinstance(v, tuple) else ("_".join("%s%s" % kv for kv in v.items()) or "default"))
+def test_no_result_depends_on_what_the_workspace_held_before_the_bind(mode, cfg, tmp_path):
+    """NETCHECK_WS_FILL: every workspace byte is 0x00 (write) or 0xff (compare: NaN as a float, UINT_MAX as an arrival counter) before
+    ocl_net_bind, in the same run-time mode -- the forms behind WC.NETCHECK_MODES (the 16x16x4 weight gradient, per-layer weight-gradient
+    launches, the dL/dy ring, the one-pass BatchNorm backward on layer 4, one stream, launch-sequence replay) over WC.NETCHECK_CASES, the
+    220-view pass of WC.NETCHECK_DEFAULT_ONLY in the default mode: not one bit of any gradient, output or running statistic differs."""
+    ref = str(tmp_path / "ref.bin")
+    rc, out = _run(cfg, "write", ref, dict(mode, NETCHECK_WS_FILL="00"))
+    assert rc == 0 and "filled with 0x00" in out, out
+    rc, out = _run(cfg, "compare", ref, dict(mode, NETCHECK_WS_FILL="ff"))
+    assert rc == 0 and "filled with 0xff" in out, out
+    m = re.search(r"(\d+) of (\d+) tensors differ in some bit", out)
+    assert m and int(m.group(1)) == 0 and int(m.group(2)) >= 60, out

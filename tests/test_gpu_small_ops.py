@@ -499,7 +499,7 @@ def test_argsort_desc_order(lib, name):
     g.check(name)
     if c["path"] == "ARGSORT_REFUSED":
         assert rc != 0
-        assert bool((d_o == Guarded.POISON).all())
+        assert bool(Guarded.is_poison(d_o).all())
         return
     ok(lib, rc, name)
     got = d_o.cpu().numpy()
@@ -525,7 +525,7 @@ def _knn_call(lib, c, ef, ey, cf, cy, what):
     g.check(what)
     order, sv = d_ord.cpu().numpy(), d_sv.cpu().numpy()
     assert np.array_equal(np.sort(order, axis=1), np.tile(np.arange(nc), (ne, 1))), "%s: a row of sorted_idx is no permutation" % what
-    assert not (sv == Guarded.POISON).any(), "%s: %d cells of sv_out were not written" % (what, int((sv == Guarded.POISON).sum()))
+    assert not Guarded.is_poison(sv).any(), "%s: %d cells of sv_out were not written" % (what, int(Guarded.is_poison(sv).sum()))
     assert np.isfinite(sv).all(), what
     return order, sv
 
@@ -588,7 +588,7 @@ def test_knn_sv_on_integer_features(lib, name):
         assert assert_path(lib, "knn", c, [d_cf]).grid_x == 0
         assert lib.ocl_knn_sv(vp(d_ef), vp(d_ey), ne, vp(d_cf), vp(d_cy), nc, dim, k, vp(d_sv), vp(d_ord), stream()) != 0
         g.check(name)
-        assert bool((d_sv == Guarded.POISON).all())
+        assert bool(Guarded.is_poison(d_sv).all())
         return
     d_sv, d_ord = g.out((ne, nc), torch.float32, 0, "sv"), g.out((ne, nc), torch.int64, 0, "order")
     assert_path(lib, "knn", c, [d_cf])
@@ -659,7 +659,7 @@ def test_ncm_class_means(lib, name):
         sel = labels == cls
         assert cnt[ci] == sel.sum()
         if not sel.any():
-            assert (got[ci] == Guarded.POISON).all(), "%s: the row of a class without samples was written" % name
+            assert Guarded.is_poison(got[ci]).all(), "%s: the row of a class without samples was written" % name
             continue
         mu = fn[sel].mean(0)
         e = 1.01 * (K + 1) * U * np.abs(fn[sel]).mean(0)
@@ -701,7 +701,7 @@ def test_ncm_predict(lib, name):
     g.check(name)
     pred = d_p.cpu().numpy()
     if n == 0:
-        assert (pred == Guarded.POISON).all()
+        assert Guarded.is_poison(pred).all()
         return
     f64 = feat.astype(np.float64)
     fn = f64 / np.linalg.norm(f64, axis=1, keepdims=True)
@@ -846,7 +846,7 @@ def _labels_outside_case(lib, op, c):
         assert np.isnan(l_bad).all(), "%s: the mean is %r" % (c["name"], l_bad.tolist())
     if dx_bad is None:
         return
-    assert not (dx_bad == Guarded.POISON).any()
+    assert not Guarded.is_poison(dx_bad).any()
     assert dx_bad[good_rows].tobytes() == dx_ok[good_rows].tobytes(), "%s: the gradient of a row with a valid label changed" % c["name"]
     for r in bad_rows:
         if op == "ce":
@@ -1002,7 +1002,7 @@ def test_supcon(lib, name):
         assert lib.ocl_supcon_fwd_bwd(vp(d_f), vp(d_y), bsz, nv, dim, T, vp(d_l), vp(d_df), vp(d_ws), stream()) != 0
         assert b"too large" in lib.ocl_last_error()
         g.check(name)
-        assert bool((d_l == Guarded.POISON).all()) and bool((d_df == Guarded.POISON).all())
+        assert bool(Guarded.is_poison(d_l).all()) and bool(Guarded.is_poison(d_df).all())
         return
     f, y = _supcon_inputs(c)
     g = Guarded()
@@ -1078,7 +1078,7 @@ def _augment_refused(lib, c):
         with pytest.raises(RuntimeError):
             ops.scr_augment_uniform(d_x, d_u, cfg, out=d_o)
     g.check(c["name"])
-    assert bool((d_o == Guarded.POISON).all()) and bool((d_par == Guarded.POISON).all())
+    assert bool(Guarded.is_poison(d_o).all()) and bool(Guarded.is_poison(d_par).all())
 
 
 @case_of("augment")
@@ -1102,7 +1102,7 @@ def test_scr_augment_against_float64(lib, name):
     ok(lib, lib.ocl_scr_augment(vp(d_x), vp(d_o), n, h, w, vp(d_p), stream()), name)
     g.check(name)
     got = d_o.cpu().numpy()
-    assert (got[n:] == Guarded.POISON).all(), "%s: output rows past n written" % name
+    assert Guarded.is_poison(got[n:]).all(), "%s: output rows past n written" % name
     if n == 0:
         return
     assert ops.scr_augment(d_x[:n], d_p[:n]).cpu().numpy().tobytes() == got[:n].tobytes()
@@ -1142,9 +1142,8 @@ def test_scr_augment_parameters_against_float64(lib, name):
     assert (plan.grid_x, plan.block) == (-(-n // 64), 64)
     ok(lib, lib.ocl_scr_augment_uniform(vp(d_x), vp(d_o), n, h, w, vp(d_u), (C.c_double * 12)(*cfg), vp(d_par), stream()), name)
     g.check(name)
-    got = d_par.cpu().numpy().astype(np.float64)
-    assert (got[n:] == Guarded.POISON).all(), "%s: parameter rows past n written" % name
-    got = got[:n]
+    assert Guarded.is_poison(d_par[n:]).all(), "%s: parameter rows past n written" % name
+    got = d_par.cpu().numpy().astype(np.float64)[:n]
     P, D = AR.ref_aug_params(u, cfg, h, w)
     rows = AR.comparable(D)
     assert (~rows).sum() <= 0.01 * n
@@ -1189,3 +1188,53 @@ CASE_TESTS = {
     "ncm_means": [test_ncm_class_means], "ncm_predict": [test_ncm_predict],
     "gemm": [test_gemm_small_is_exact_on_integers, test_gemm_small_random_within_fp32_bound],
 }
+
+
+# ==========================================================================================================================================
+# the NaN leg: one case per distinct path code of the table
+# ==========================================================================================================================================
+def nan_leg_cases():
+    """(op, case name): the first case of the table for every distinct `path` code."""
+    seen, rows = set(), []
+    for op, cases in SC.CASES.items():
+        for c in cases:
+            if c["path"] not in seen:
+                seen.add(c["path"])
+                rows.append((op, c["name"]))
+    return rows
+
+
+@pytest.mark.parametrize("op,name", nan_leg_cases(), ids=lambda v: v)
+def test_nan_leg_equals_the_finite_leg(lib, op, name):
+    """The case's tests once more with every output, workspace and guard region holding 0xFFFFFFFF (integer tensors: their minimum) instead
+    of -7777 / 4096 (guarded.run_both_legs): the tests' own assertions hold, and every output is bit-identical in the two legs.  A kernel
+    that reads what it has not written -- a workspace assumed zero, an element past a tensor's end times zero -- differs there."""
+    from guarded import run_both_legs
+    n0, n1 = len(REPORT), len(AUG_REPORT)
+    try:
+        for fn in CASE_TESTS[op]:
+            run_both_legs(lambda: fn(lib, name), "%s/%s/%s" % (op, name, fn.__name__))
+    finally:
+        del REPORT[n0:], AUG_REPORT[n1:]       # (the parity report holds the module's own run of the case, once)
+
+
+def test_the_nan_leg_sees_a_read_of_unwritten_memory(cuda):
+    """guarded.run_both_legs on two stand-in "kernels": one that stores its output passes; one that forms 0 * (what the output held) + x
+    -- right over -7777, NaN over 0xFFFFFFFF -- is reported, as is one that leaves a cell unwritten in one leg only."""
+    from guarded import run_both_legs
+
+    def body(kind):
+        g = Guarded()
+        x, o = g.inp(np.arange(8, dtype=np.float32), 3, "x"), g.out((8,), torch.float32, 1, "o")
+        if kind == "stores":
+            o.copy_(x)
+        elif kind == "reads":
+            o.mul_(0.0).add_(x)
+        elif Guarded.LEG == "nan":
+            o[:4].copy_(x[:4])
+        g.check(kind)
+
+    run_both_legs(lambda: body("stores"), "stores")
+    for kind in ("reads", "one_leg"):
+        with pytest.raises(AssertionError, match="differs between the legs"):
+            run_both_legs(lambda: body(kind), kind)

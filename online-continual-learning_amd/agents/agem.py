@@ -6,14 +6,11 @@ point apart] -> opt.step -> buffer.update.  The reference keeps the two gradient
 with one small reduction per tensor and asks the host `if prod < 0`.  Here both gradients are flat arrays: the batch gradient is
 moved aside with one device copy, the memory pass overwrites the flat gradient array, and `ops.agem_project` (two launches, no
 synchronisation) leaves what opt.step() reads next in that array."""
-import contextlib
-
 import torch
 
 from .. import debug
 from .. import ops
 from ..buffer import Buffer
-from ..data import DeviceLoader
 from ..utils import maybe_cuda, AverageMeter
 from ..loss import unit_gradient
 from .base import ContinualLearner
@@ -31,11 +28,6 @@ class AGEM(ContinualLearner):
         self._g_batch = self._info = None   # the batch gradient beside the flat gradient array; what the projection decided
 
     # ---- pieces of a step ----------------------------------------------------------------------------------------------
-    @staticmethod
-    def _emit(tag, loss):
-        if debug.on():
-            debug.emit(tag, loss=float(loss.detach()))
-
     def _memory_pass(self, mem_x, mem_y):
         mem_logits = self.model.forward(mem_x)
         loss_mem = self.criterion(mem_logits, mem_y)
@@ -76,11 +68,7 @@ class AGEM(ContinualLearner):
     def _step(self, batch_x, batch_y, meters):
         logits = self.model.forward(batch_x)
         loss = self._kd_mix(self.criterion(logits, batch_y), logits, batch_x)
-        if self.verbose:      # (the reference's per-iteration .item() would stall the stream)
-            loss_meter, acc_meter = meters
-            hits = (torch.max(logits, 1)[1] == batch_y).sum()
-            acc_meter.update(hits / batch_y.size(0), batch_y.size(0))
-            loss_meter.update(loss, batch_y.size(0))
+        self._track(meters, logits, batch_y, loss)
         self._emit("agem_loss", loss)
         self.opt.zero_grad()
         loss.backward(unit_gradient(loss))
@@ -97,23 +85,12 @@ class AGEM(ContinualLearner):
         self.opt.step()
 
     # ---- the loop ------------------------------------------------------------------------------------------------------
-    def train_learner(self, x_train, y_train):
-        same = self.model.same_weights() if hasattr(self.model, "same_weights") else contextlib.nullcontext()
-        with self.launch_stream(), same:
-            self._train_learner(x_train, y_train)
-
     def _train_learner(self, x_train, y_train):
-        self.before_train(x_train, y_train)
-        # device-resident task behind the reference's DataLoader (same sampler, same RNG draws)
-        train_loader = DeviceLoader(x_train, y_train, self.batch, shuffle=True, drop_last=True)
-        self.model = self.model.train()
         meters = (AverageMeter(), AverageMeter())
-        for ep in range(self.epoch):
-            for i, (batch_x, batch_y) in enumerate(train_loader):
-                batch_y_host = train_loader.last_y_host
+        for batches in self._epochs(x_train, y_train):
+            for i, batch_x, batch_y, batch_y_host in batches:
                 for j in range(self.mem_iters):
                     self._step(batch_x, batch_y, meters)
                 self.buffer.update(batch_x, batch_y, y_host=batch_y_host)
-                if i % 100 == 1 and self.verbose:
-                    print('==>>> it: {}, avg. loss: {:.6f}, running train acc: {:.3f}'.format(i, meters[0].avg(), meters[1].avg()))
+                self._print_running(i, meters)
         self.after_train()

@@ -2,9 +2,12 @@
 evaluate() with the nearest-class-mean classifier (NCM) or argmax, on the MI355X.
 
 The labels trick and the separated softmax share one segmented cross-entropy kernel; the KD tricks use ocl_kd_fwd_bwd with a
-parameter-snapshot teacher (kd_manager.py)."""
-from abc import abstractmethod
+parameter-snapshot teacher (kd_manager.py).
+
+It also owns what the agents' loops share ("The agents' loop skeleton"): train_learner, the prologue and batch iteration
+(_epochs), the verbose meters (_track, _print_running), the loss trace (_emit) and the predicate _taped_ce_ok."""
 import abc
+import contextlib
 import copy
 import pickle
 
@@ -13,6 +16,7 @@ import torch
 
 from .. import ops
 from .. import debug
+from ..data import DeviceLoader
 from ..loss import SupConLoss, cross_entropy_mean, cross_entropy_segmented_mean, unit_gradient
 from ..kd_manager import KdManager
 from ..error_analysis import ErrorAnalysis, TorchErrorAnalysis
@@ -54,7 +58,10 @@ class ContinualLearner(torch.nn.Module, metaclass=abc.ABCMeta):
                 "branch reads the `logits` its NCM path never computes, and compares indices into old_labels with class labels")
 
     _gc_frozen = False
+    _same_weights = True                   # train_learner runs the loop inside model.same_weights() (False: SCR, one forward per step; GDumb, whose loop replaces self.model)
     _force_torch_error_analysis = False    # the error analysis by per-tensor torch operations and host reads (the comparator of the fused path)
+    _force_autograd = False                # the A/Bs' and the tests' comparator: the loss through criterion / torch ops and autograd instead of the taped backward
+    _force_losses = False                  # ER, ASER mode: run the losses of passes 1 and 2 although nobody reads them (_passes_12_have_readers)
 
     def _predicts_by_ncm(self):
         return self.params.trick['ncm_trick'] or self.params.agent in ['ICARL', 'SCR', 'SCP']
@@ -89,15 +96,76 @@ class ContinualLearner(torch.nn.Module, metaclass=abc.ABCMeta):
         for i in new_labels:
             self.class_task_map[i] = self.task_seen
 
-    @abstractmethod
+    # ---- what every agent's loop shares --------------------------------------------------------------------------------------------
     def train_learner(self, x_train, y_train):
-        pass
+        """One task: the agent's `_train_learner` inside launch_stream() and, where `_same_weights` says so, model.same_weights():
+        between two optimiser steps every forward of the loop reads the same weights (ASER mode: five of them per iteration), and
+        inside that block the engine packs them once per step (resnet.py; writes by anybody else are detected, not assumed away)."""
+        with self.launch_stream(), (self.model.same_weights() if self._same_weights else contextlib.nullcontext()):
+            self._train_learner(x_train, y_train)
+
+    def _train_learner(self, x_train, y_train):
+        raise NotImplementedError
+
+    def _epochs(self, x_train, y_train, epochs=None, train=True, data=None):
+        """The loop's prologue -- before_train, the device-resident task behind the reference's DataLoader (same sampler, same RNG
+        draws), the model in train mode -- done at the call; returns an iterable with one iterable of (i, batch_x, batch_y, batch_y_host)
+        per epoch.  `data` (agents/_streams.py) is opened behind the prologue, and the loader's gathers are issued on its stream."""
+        self.before_train(x_train, y_train)
+        train_loader = DeviceLoader(x_train, y_train, self.batch, shuffle=True, drop_last=True)
+        if train:
+            self.model = self.model.train()
+        on_data = contextlib.nullcontext
+        if data is not None:
+            data.open()
+            on_data = data.on_data
+
+        def batches():
+            loader_it = iter(train_loader)
+            i = 0
+            while True:
+                with on_data():
+                    batch_data = next(loader_it, None)
+                if batch_data is None:
+                    return
+                yield i, batch_data[0], batch_data[1], train_loader.last_y_host
+                i += 1
+
+        return (batches() for ep in range(self.epoch if epochs is None else epochs))
+
+    def _track(self, meters, logits, labels, value):
+        """Running loss / accuracy (only when printing: the reference's per-iteration .item() would stall the stream).  `meters` is
+        (loss meter, accuracy meter); logits=None records the loss alone."""
+        if not self.verbose:
+            return
+        loss_meter, acc_meter = meters
+        if logits is not None:
+            hits = (torch.max(logits, 1)[1] == labels).sum()
+            acc_meter.update(hits / labels.size(0), labels.size(0))
+        loss_meter.update(value, labels.size(0))
+
+    _running_format = '==>>> it: {}, {}avg. loss: {:.6f}, running {}acc: {:.3f}'
+
+    def _print_running(self, i, meters, tag=""):
+        if i % 100 == 1 and self.verbose:
+            print(self._running_format.format(i, tag, meters[0].avg(), tag or "train ", meters[1].avg()))
+
+    @staticmethod
+    def _emit(tag, loss, **more):
+        """A debug event of a step's loss (and further scalars): each value is fetched -- a host synchronisation -- only when tracing."""
+        if debug.on():
+            debug.emit(tag, loss=float(loss.detach()), **{k: float(v.detach()) if torch.is_tensor(v) else float(v) for k, v in more.items()})
+
+    def _taped_ce_ok(self):
+        """Plain cross-entropy (agents/base.py:113) on the engine's taped backward: the loss kernel's dL/dlogits may go straight into
+        model.backward_taped, without autograd between the two."""
+        trick = self.params.trick
+        return not trick['labels_trick'] and not trick['separated_softmax'] and not self._force_autograd
 
     def launch_stream(self):
         """Context for the training loop.  With launch-sequence replay requested (OCL_GRAPH=1, csrc/net.hip run_replayed) the loop runs
         on a stream of its own, ordered after and before the caller's stream: hipStreamBeginCapture is refused on the default stream,
         and the replay is what keeps a host-bound loop (ER + ASER: one synchronisation per step) from waiting on launch calls."""
-        import contextlib
         import os
 
         @contextlib.contextmanager
@@ -161,7 +229,8 @@ class ContinualLearner(torch.nn.Module, metaclass=abc.ABCMeta):
     def _step_scaled(self, scale):
         if hasattr(self.opt, "model"):
             self.opt.step(grad_scale=scale)
-        else:
+        else:   # a stock torch optimiser: setup_opt never returns one, scripts/adam_step_ab.py builds its comparator around one
+
             for p in self.model.parameters():
                 if p.requires_grad and p.grad is not None:
                     p.grad.data.mul_(scale)

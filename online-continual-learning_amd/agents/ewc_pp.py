@@ -7,13 +7,10 @@ its global min and max.  The reference holds all of that as four dictionaries of
 penalty.  Here the four are flat arrays beside model.flat_params(): the penalty's gradient 2 * lambda * w * f_hat * (p - p_prev) and
 the Fisher accumulation are one launch on the flat gradient array (`ops.ewc_accumulate`), the moving average one launch
 (`ops.ewc_fisher_ema`), the normalisation two (`ops.ewc_fisher_normalize`).  There is no replay memory."""
-import contextlib
-
 import torch
 
 from .. import debug
 from .. import ops
-from ..data import DeviceLoader
 from ..utils import AverageMeter
 from ..loss import unit_gradient
 from .base import ContinualLearner
@@ -109,14 +106,9 @@ class EWC_pp(ContinualLearner):
                                penalty_out=self._penalty if (want and seen) else None)
             if want and seen:
                 penalty = self._penalty[0]
-        if self.verbose:      # (the reference's per-iteration .item() would stall the stream)
-            loss_meter, acc_meter = meters
-            hits = (torch.max(logits, 1)[1] == batch_y).sum()
-            acc_meter.update(hits / batch_y.size(0), batch_y.size(0))
-            total = loss.detach() if penalty is None else loss.detach() + (w * self.lambda_) * penalty
-            loss_meter.update(total, batch_y.size(0))
-        if debug.on():
-            debug.emit("ewc_loss", loss=float(loss.detach()), penalty=0.0 if penalty is None else float(penalty))
+        if self.verbose:
+            self._track(meters, logits, batch_y, loss.detach() if penalty is None else loss.detach() + (w * self.lambda_) * penalty)
+        self._emit("ewc_loss", loss, penalty=0.0 if penalty is None else penalty)
         self.opt.step()
 
     def _task_end(self):
@@ -133,25 +125,22 @@ class EWC_pp(ContinualLearner):
             debug.emit("ewc_task_end", min_fisher=lo, max_fisher=hi)
 
     # ---- the loop ------------------------------------------------------------------------------------------------------------------
-    def train_learner(self, x_train, y_train):
-        same = self.model.same_weights() if hasattr(self.model, "same_weights") else contextlib.nullcontext()
-        with self.launch_stream(), same:
-            self._train_learner(x_train, y_train)
+    def before_train(self, x_train, y_train):
+        """The flat arrays exist before the task is moved to the device (a model moved after the constructor: allocated here)."""
+        super(EWC_pp, self).before_train(x_train, y_train)
+        self._ensure_state()
 
     def _train_learner(self, x_train, y_train):
-        self.before_train(x_train, y_train)
-        self._ensure_state()
-        # device-resident task behind the reference's DataLoader (same sampler, same RNG draws)
-        train_loader = DeviceLoader(x_train, y_train, self.batch, shuffle=True, drop_last=True)
-        self.model = self.model.train()
         meters = (AverageMeter(), AverageMeter())
-        for ep in range(self.epoch):
-            for i, (batch_x, batch_y) in enumerate(train_loader):
-                # update the running fisher (:41-42): the counter restarts with every call, the temporary Fisher does not
-                if (ep * len(train_loader) + i + 1) % self.fisher_update_after == 0:
+        it = 0
+        for batches in self._epochs(x_train, y_train):
+            for i, batch_x, batch_y, _ in batches:
+                # update the running fisher (:41-42, (ep * len(train_loader) + i + 1) % fisher_update_after): the count of the call's
+                # iterations restarts with every call, the temporary Fisher does not
+                it += 1
+                if it % self.fisher_update_after == 0:
                     self._update_running_fisher()
                 self._step(batch_x, batch_y, meters)
-                if i % 100 == 1 and self.verbose:
-                    print('==>>> it: {}, avg. loss: {:.6f}, running train acc: {:.3f}'.format(i, meters[0].avg(), meters[1].avg()))
+                self._print_running(i, meters)
         self._task_end()
         self.after_train()

@@ -8,7 +8,6 @@ sequence of model / RNG / buffer effects and chooses a cheaper schedule where th
 * ASER mode (`_two_pass_step`): the gradients of the first two passes are thrown away by the reference's zero_grad(), so their
   backward is not run (MIR retrieval still gets the batch pass's gradient vector).
 """
-import contextlib
 import os
 
 import numpy as np
@@ -17,9 +16,9 @@ import torch
 from .. import debug
 from .. import ops
 from ..buffer import Buffer
-from ..data import DeviceLoader
 from ..utils import maybe_cuda, AverageMeter
 from ..loss import unit_gradient
+from ._streams import DataStream
 from .base import ContinualLearner
 
 
@@ -32,27 +31,11 @@ class ExperienceReplay(ContinualLearner):
         self.mem_iters = params.mem_iters
 
     # ---- pieces of a step ----------------------------------------------------------------------------------------------
-    def _track(self, meters, logits, labels, loss):
-        """Running loss / accuracy (only when printing: the reference's per-iteration .item() would stall the stream)."""
-        if not self.verbose:
-            return
-        loss_meter, acc_meter = meters
-        hits = (torch.max(logits, 1)[1] == labels).sum()
-        acc_meter.update(hits / labels.size(0), labels.size(0))
-        loss_meter.update(loss, labels.size(0))
-
-    @staticmethod
-    def _emit(tag, loss):
-        if debug.on():
-            debug.emit(tag, loss=float(loss.detach()))
-
     def _merged_step(self, batch_x, batch_y, mem_x, mem_y, meters):
         """Batch pass + memory pass as one pass with two BatchNorm groups (statistics and running-stat updates per group, in
         order); the two CE losses are back-propagated together, which is what two backward() calls into the same gradients sum to."""
         n = batch_x.size(0)
-        trick = self.params.trick
-        if (hasattr(self.model, "forward_views_taped") and not trick['labels_trick'] and not trick['separated_softmax']
-                and self.params.agent not in ('SCR', 'SCP') and not getattr(self, "_force_autograd", False)):   # (_force_autograd: the A/B test)
+        if self._taped_ce_ok() and self.params.agent not in ('SCR', 'SCP'):
             # plain cross-entropy (agents/base.py:113): the two losses write their dL/dlogits into the two row blocks of ONE buffer and
             # the engine's backward takes it as it is -- the same numbers autograd would assemble with two slice-backward fills, two
             # copies and an add (six tiny launches on the dependent chain of a 0.9 ms step)
@@ -89,7 +72,7 @@ class ExperienceReplay(ContinualLearner):
         weights, statistics and memory bit for bit."""
         trick = self.params.trick
         return (not aser or self.params.retrieve == 'MIR' or self.verbose or debug.on() or trick['kd_trick'] or trick['kd_trick_star']
-                or getattr(self, "_force_losses", False) or not hasattr(self.model, "forward_stats_only"))
+                or self._force_losses)
 
     def _two_pass_step(self, batch_x, batch_y, batch_y_host, meters, aser, retrieved=None, logits=None):
         back12 = not aser or self.params.retrieve == 'MIR'   # MIR reads the batch pass's gradient
@@ -128,9 +111,7 @@ class ExperienceReplay(ContinualLearner):
             if getattr(mem_y, 'host', None) is not None:
                 combined_labels.host = np.concatenate((np.asarray(mem_y.host), np.asarray(batch_y_host)))
             # (torch.cat((mem_x, batch_x)) is not materialised: the engine reads the two pieces where they are)
-            trick = self.params.trick
-            if (hasattr(self.model, "forward_views_taped") and not trick['labels_trick'] and not trick['separated_softmax']
-                    and not getattr(self, "_force_autograd", False) and os.environ.get("OCL_ASER_AUTOGRAD", "0") != "1"):   # (both: the A/B's autograd side)
+            if self._taped_ce_ok() and os.environ.get("OCL_ASER_AUTOGRAD", "0") != "1":   # (the switch: the A/B's autograd side)
                 # plain cross-entropy (agents/base.py:113), as in _merged_step: the loss kernel's dL/dlogits goes straight into the engine's
                 # backward -- the same numbers, without autograd's engine between the loss and the backward (a hand-over to its worker
                 # thread with the GPU's queue already empty: ~0.1 ms of an ASER step, profiles/r6_aser_step_timeline.txt)
@@ -145,20 +126,7 @@ class ExperienceReplay(ContinualLearner):
         self.opt.step()
 
     # ---- the loop ------------------------------------------------------------------------------------------------------
-    def train_learner(self, x_train, y_train):
-        # Between two optimiser steps every forward of the loop reads the same weights (ASER mode: five of them per iteration): inside
-        # model.same_weights() the engine packs them once per step (resnet.py; writes by anybody else are detected, not assumed away)
-        same = self.model.same_weights() if hasattr(self.model, "same_weights") else contextlib.nullcontext()
-        with self.launch_stream(), same:
-            self._train_learner(x_train, y_train)
-
     def _train_learner(self, x_train, y_train):
-        self.before_train(x_train, y_train)
-        # device-resident task behind the reference's DataLoader (same sampler, same RNG draws)
-        train_loader = DeviceLoader(x_train, y_train, self.batch, shuffle=True, drop_last=True)
-        self.model = self.model.train()
-        meters = ((AverageMeter(), AverageMeter()), (AverageMeter(), AverageMeter()))   # (loss, acc) of batch / memory passes
-
         trick = self.params.trick
         aser = self.params.update == 'ASER' or self.params.retrieve == 'ASER'
         # Random retrieval reads neither the model nor its gradients and nothing between the batch forward and the retrieval draws
@@ -174,32 +142,15 @@ class ExperienceReplay(ContinualLearner):
                     and not trick['kd_trick'] and not trick['kd_trick_star'] and hasattr(upd, "update_begin")
                     and os.environ.get("OCL_ASER_PIPELINE", "1") != "0")
 
-        # Random retrieval + reservoir update never touch the model: like agents/scr.py, the data path (loader gather, retrieve gather,
-        # reservoir scatter: ~20 tiny launches, 5 % of a 1 ms step) goes to its own stream, so that step i+1's data work runs next to
-        # step i's backward instead of in front of step i+1's forward.  Same statements, same order, same RNG draws (OCL_DATA_STREAM=0:
-        # everything on the main stream; tests/test_gpu_steps.py::test_er_data_stream_overlap_is_schedule_only: bit-identical end state).
-        overlap = (merge and self.cuda and self.params.update == 'random' and not debug.on()
-                   and os.environ.get("OCL_DATA_STREAM", "1") != "0")
-        main = torch.cuda.current_stream() if self.cuda else None
-        ds = ops.data_stream(x_train.device if torch.is_tensor(x_train) and x_train.is_cuda else torch.cuda.current_device()) if overlap else None
-        if overlap:
-            ds.wait_stream(main)
+        # Random retrieval + reservoir update never touch the model: like agents/scr.py, the data path goes to its own stream
+        # (agents/_streams.py; tests/test_gpu_steps.py::test_er_data_stream_overlap_is_schedule_only: bit-identical end state).
+        data = DataStream(merge and self.cuda and self.params.update == 'random' and not debug.on(), x_train)
+        on_data = data.on_data
+        meters = ((AverageMeter(), AverageMeter()), (AverageMeter(), AverageMeter()))   # (loss, acc) of batch / memory passes
 
-        def on_data():
-            return torch.cuda.stream(ds) if overlap else contextlib.nullcontext()
-
-        for ep in range(self.epoch):
+        for batches in self._epochs(x_train, y_train, data=data):
             pending = None
-            loader_it = iter(train_loader)
-            i = -1
-            while True:
-                with on_data():
-                    batch_data = next(loader_it, None)
-                if batch_data is None:
-                    break
-                i += 1
-                batch_x, batch_y = batch_data
-                batch_y_host = train_loader.last_y_host
+            for i, batch_x, batch_y, batch_y_host in batches:
                 pre = None
                 if pipeline:
                     # (same weights as update_begin's feature pass, which read the stepped weights first)
@@ -216,10 +167,7 @@ class ExperienceReplay(ContinualLearner):
                         with on_data():
                             retrieved = self.buffer.retrieve(x=batch_x, y=batch_y)
                             retrieved = (maybe_cuda(retrieved[0], self.cuda), maybe_cuda(retrieved[1], self.cuda))
-                        if overlap:
-                            main.wait_stream(ds)
-                            for t in (batch_x, batch_y) + retrieved:
-                                t.record_stream(main)   # allocated on the data stream, consumed on the main one
+                        data.hand_over(batch_x, batch_y, *retrieved)
                         if retrieved[0].size(0) == batch_x.size(0):
                             self._merged_step(batch_x, batch_y, retrieved[0], retrieved[1], meters)
                             continue
@@ -231,12 +179,9 @@ class ExperienceReplay(ContinualLearner):
                     with on_data():
                         self.buffer.update(batch_x, batch_y, y_host=batch_y_host)
 
-                if i % 100 == 1 and self.verbose:
-                    for tag, (loss_meter, acc_meter) in zip(("", "mem "), meters):
-                        print('==>>> it: {}, {}avg. loss: {:.6f}, running {}acc: {:.3f}'.format(i, tag, loss_meter.avg(), "mem " if tag else "train ",
-                                                                                             acc_meter.avg()))
+                self._print_running(i, meters[0])
+                self._print_running(i, meters[1], "mem ")
             if pipeline:
                 upd.update_finish(self.buffer, pending)
-        if overlap:
-            main.wait_stream(ds)
+        data.join()
         self.after_train()

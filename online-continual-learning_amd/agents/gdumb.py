@@ -14,7 +14,6 @@ import torch
 
 from .. import debug
 from .. import ops
-from ..data import DeviceLoader
 from ..gdumb_memory import GdumbMemory
 from ..loss import unit_gradient
 from ..setup_elements import setup_architecture, setup_opt, input_size_match
@@ -23,6 +22,7 @@ from .base import ContinualLearner
 
 
 class Gdumb(ContinualLearner):
+    _same_weights = False       # train_mem() replaces self.model: the context of the network it lets go must not wrap the call
     _force_torch_clip = False   # the A/B's and one test's comparator: torch.nn.utils.clip_grad_norm_ over the p.grad views (:82 as written)
 
     def __init__(self, model, opt, params):
@@ -51,8 +51,8 @@ class Gdumb(ContinualLearner):
             total = ops.clip_grad_norm_(grads, self.clip, info=self._info)
         opt.step()
         self.mem_steps += 1
+        self._emit("gdumb_loss", loss)
         if debug.on():
-            debug.emit("gdumb_loss", loss=float(loss.detach()))
             if self._force_torch_clip:
                 total = float(total)
                 coef = min(self.clip / (total + 1e-6), 1.0)
@@ -98,17 +98,12 @@ class Gdumb(ContinualLearner):
                 meter = []
 
     # ---- the loop (:33-50) -----------------------------------------------------------------------------------------------
-    def train_learner(self, x_train, y_train):
-        with self.launch_stream():
-            self._train_learner(x_train, y_train)
-
     def _train_learner(self, x_train, y_train):
-        self.before_train(x_train, y_train)
-        # device-resident task behind the reference's DataLoader (same sampler, same RNG draws)
-        train_loader = DeviceLoader(x_train, y_train, self.batch, shuffle=True, drop_last=True)
-        for i, (batch_x, batch_y) in enumerate(train_loader):
-            if self.memory is None:
-                self.memory = GdumbMemory(self.params.mem_size, input_size_match[self.data], batch_x.device, batch=self.batch)
-            self.memory.update(batch_x, train_loader.last_y_host)
+        # one pass over the stream, which only feeds the memory: the network on hand is not trained, and not put in train mode
+        for batches in self._epochs(x_train, y_train, epochs=1, train=False):
+            for i, batch_x, batch_y, batch_y_host in batches:
+                if self.memory is None:
+                    self.memory = GdumbMemory(self.params.mem_size, input_size_match[self.data], batch_x.device, batch=self.batch)
+                self.memory.update(batch_x, batch_y_host)
         self.train_mem()
         self.after_train()

@@ -13,23 +13,18 @@ on the host from the loader's label mirror, forwards the student over (stream ba
 on a tape, forwards the teacher's parameter snapshot over the same two pieces, and gets the three losses and dL/dlogits from ONE launch
 (`ops.bce_distill`), which the engine's backward takes as it is.  The label tricks and the KD tricks do not enter iCaRL's loss in the
 reference, and not here; `review_trick` and `ncm_trick` take base.py's paths."""
-import contextlib
-
 import torch
 from torch.nn import functional as F
 
 from .. import debug
 from .. import ops
 from ..buffer import Buffer
-from ..data import DeviceLoader
 from ..kd_manager import KdManager
 from ..plugins.buffer_utils import random_retrieve
 from .base import ContinualLearner
 
 
 class Icarl(ContinualLearner):
-    _force_autograd = False   # the A/B's and one test's comparator: the reference's statements over torch ops and autograd
-
     def __init__(self, model, opt, params):
         super(Icarl, self).__init__(model, opt, params)
         self.mem_size = params.mem_size
@@ -37,7 +32,8 @@ class Icarl(ContinualLearner):
         self.prev = KdManager()   # the reference's prev_model (:31): a snapshot of its own, apart from the KD tricks' kd_manager
 
     def _fused(self):
-        return hasattr(self.model, "forward_views_taped") and not self._force_autograd
+        # (not _taped_ce_ok(): its other two terms are the label tricks, which do not enter iCaRL's loss)
+        return not self._force_autograd
 
     def _positions(self, y_host):
         """The batch's labels as target columns (:43-44): len(old_labels) + new_labels.index(y); ValueError for a label that is not
@@ -96,24 +92,15 @@ class Icarl(ContinualLearner):
             loss.backward()
         self.opt.step()
 
-    def train_learner(self, x_train, y_train):
-        same = self.model.same_weights() if hasattr(self.model, "same_weights") else contextlib.nullcontext()
-        with self.launch_stream(), same:
-            self._train_learner(x_train, y_train)
-
     def _train_learner(self, x_train, y_train):
-        self.before_train(x_train, y_train)
-        # device-resident task behind the reference's DataLoader (same sampler, same RNG draws)
-        train_loader = DeviceLoader(x_train, y_train, self.batch, shuffle=True, drop_last=True)
-        self.model = self.model.train()
-        self.update_representation(train_loader)
+        self.update_representation(self._epochs(x_train, y_train))
         self.prev.update_teacher(self.model)      # prev_model = copy.deepcopy(model) (:31), before after_train's review steps
         self.after_train()
 
     def update_representation(self, train_loader):
+        """`train_loader`: the epochs of ContinualLearner._epochs."""
         updated_idx = []
-        for ep in range(self.epoch):
-            for i, (train_x, train_y) in enumerate(train_loader):
-                y_host = train_loader.last_y_host
+        for batches in train_loader:
+            for i, train_x, train_y, y_host in batches:
                 self._step(train_x, train_y, y_host, updated_idx)
                 updated_idx += self.buffer.update(train_x, train_y, y_host=y_host)

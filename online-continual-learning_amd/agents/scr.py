@@ -3,19 +3,17 @@
 Per iteration: retrieve -> concat -> augment -> two views through SupConResNet -> SupCon loss -> SGD ->
 reservoir update.  The two views run as one batched pass with per-view BatchNorm statistics (the reference
 calls model.forward twice, scr.py:55)."""
-import contextlib
 import math
-import os
 
 import torch
 
 from .. import ops
 from .. import debug
 from ..buffer import Buffer
-from ..data import DeviceLoader
 from ..setup_elements import input_size_match
 from ..utils import maybe_cuda, AverageMeter
 from ..loss import unit_gradient
+from ._streams import DataStream
 from .base import ContinualLearner
 
 
@@ -124,6 +122,9 @@ class ScrAugment(object):
 
 
 class SupContrastReplay(ContinualLearner):
+    _same_weights = False                                      # one forward per step: nothing to share between two optimiser steps
+    _running_format = '==>>> it: {0}, avg. loss: {2:.6f}, '    # the reference's line: no accuracy, and it ends in ", "
+
     def __init__(self, model, opt, params):
         super(SupContrastReplay, self).__init__(model, opt, params)
         self.buffer = Buffer(model, params)
@@ -133,48 +134,15 @@ class SupContrastReplay(ContinualLearner):
         self.transform = ScrAugment(size=(input_size_match[self.params.data][1], input_size_match[self.params.data][2]),
                                     scale=(0.2, 1.))
 
-    def train_learner(self, x_train, y_train):
-        with self.launch_stream():
-            self._train_learner(x_train, y_train)
-
     def _train_learner(self, x_train, y_train):
-        self.before_train(x_train, y_train)
-        # set up loader
-        train_loader = DeviceLoader(x_train, y_train, self.batch, shuffle=True, drop_last=True)
-        # set up model
-        self.model = self.model.train()
+        meters = (AverageMeter(), AverageMeter())   # (loss, acc); nothing records an accuracy
 
-        # setup tracker
-        losses = AverageMeter()
-        acc_batch = AverageMeter()
+        # Data path on its own stream (random retrieve / reservoir update only: they never touch the model; agents/_streams.py)
+        data = DataStream(self.cuda and self.params.retrieve == 'random' and self.params.update == 'random' and not debug.on(), x_train)
+        on_data = data.on_data
 
-        # Data path on its own stream (random retrieve / reservoir update only: they never touch the model).  Same statements, same
-        # order, same RNG draws as the reference's loop; only the stream they are issued on differs, so that the gather / concat /
-        # augment / scatter launches of step i+1 (~20 tiny launches, ~0.15 ms back to back) run next to step i's backward instead
-        # of in front of step i+1's forward.
-        overlap = (self.cuda and self.params.retrieve == 'random' and self.params.update == 'random' and not debug.on()
-                   and os.environ.get("OCL_DATA_STREAM", "1") != "0")
-        main = torch.cuda.current_stream() if self.cuda else None
-        ds = ops.data_stream(x_train.device if torch.is_tensor(x_train) and x_train.is_cuda else torch.cuda.current_device()) if overlap else None
-        if overlap:
-            ds.wait_stream(main)
-
-        def on_data():
-            return torch.cuda.stream(ds) if overlap else contextlib.nullcontext()
-
-        for ep in range(self.epoch):
-            loader_it = iter(train_loader)
-            i = -1
-            while True:
-                with on_data():
-                    batch_data = next(loader_it, None)
-                if batch_data is None:
-                    break
-                i += 1
-                # batch update
-                batch_x, batch_y = batch_data
-                batch_y_host = train_loader.last_y_host
-
+        for batches in self._epochs(x_train, y_train, data=data):
+            for i, batch_x, batch_y, batch_y_host in batches:
                 for j in range(self.mem_iters):
                     with on_data():
                         mem_x, mem_y = self.buffer.retrieve(x=batch_x, y=batch_y)
@@ -193,16 +161,11 @@ class SupContrastReplay(ContinualLearner):
                                 first_view = (torch.cat((mem_x, batch_x)),)
                                 aug = self.transform(first_view[0])
                             second_view = tuple(aug) if isinstance(aug, (tuple, list)) else (aug,)
-                        if overlap:
-                            main.wait_stream(ds)
-                            for t in first_view + second_view + (combined_labels,):
-                                t.record_stream(main)   # allocated on the data stream, consumed on the main one
+                        data.hand_over(*first_view, *second_view, combined_labels)
                         features = self.model.forward_views([first_view, second_view])
                         loss = self.criterion_views(features, combined_labels, 2)
-                        if self.verbose:
-                            losses.update(loss, batch_y.size(0))
-                        if debug.on():
-                            debug.emit("scr_loss", loss=float(loss.detach()))
+                        self._track(meters, None, batch_y, loss)
+                        self._emit("scr_loss", loss)
                         self.opt.zero_grad()
                         loss.backward(unit_gradient(loss))
                         self.opt.step()
@@ -210,11 +173,7 @@ class SupContrastReplay(ContinualLearner):
                 # update mem
                 with on_data():
                     self.buffer.update(batch_x, batch_y, y_host=batch_y_host)
-                if i % 100 == 1 and self.verbose:
-                        print(
-                            '==>>> it: {}, avg. loss: {:.6f}, '
-                                .format(i, losses.avg(), acc_batch.avg())
-                        )
-        if overlap:
-            main.wait_stream(ds)
+                self._print_running(i, meters)
+        data.join()
         self.after_train()
+

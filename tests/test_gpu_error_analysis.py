@@ -15,9 +15,10 @@ import numpy as np
 import pytest
 import torch
 
+from agent_harness import build_agent, dev as _dev, host as _host, bits as _bits, rng_get as _rng_get, rng_set as _rng_set
 from conftest import gold
 from guarded import Guarded
-from oracle.synth import make_stream, seed_all, case_params
+from oracle.synth import make_stream
 import parity_bounds
 import error_analysis_ref as E
 from error_analysis_ref import ref_row_argmax_groupsum, ref_error_analysis, ref_norms
@@ -33,8 +34,6 @@ SHAPES = [
     (100, 160), (100, 640),                           # the last layer's weight
 ]
 SCALES = [1e-3, 1.0, 1e3]
-TRICK = {'labels_trick': False, 'kd_trick': False, 'separated_softmax': False, 'review_trick': False, 'ncm_trick': False,
-         'kd_trick_star': False}
 POISON = -7777
 
 
@@ -49,18 +48,6 @@ def _parity_report():
             for case, tensor, err, e_ref, bound, ratio in REPORT:
                 f.write("%-52s %-8s %-12.4g %-12s %-12.4g %.3f\n" % (case, tensor, err, e_ref, bound, ratio))
             f.write("worst err/bound %.3f over %d rows\n" % (max(r[5] for r in REPORT), len(REPORT)))
-
-
-def _dev(a, cuda, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(cuda)
-
-
-def _host(t):
-    return t.detach().cpu().numpy()
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int64 if t.element_size() == 8 else torch.int32)
 
 
 def _x(n, c, scale):
@@ -287,31 +274,6 @@ def test_recorded_logits_through_the_pipeline_reproduce_the_recorded_outputs(cud
 LISTS = ("error_list", "new_class_score", "old_class_score", "fc_norm_new", "fc_norm_old", "bias_norm_new", "bias_norm_old")
 
 
-def _build_agent(cfg, **over):
-    from ocl_amd import name_match
-    from ocl_amd.setup_elements import setup_architecture, setup_opt
-    p = dict(agent="ER", retrieve="random", update="random", data="cifar10", mem_size=50, eps_mem_batch=10, cuda=True, epoch=1,
-             batch=10, test_batch=E.EA_TEST_BATCH, verbose=False, optimizer="SGD", learning_rate=0.1, weight_decay=0, mem_iters=1, subsample=50, k=3,
-             aser_type="asvm", n_smp_cls=1.5, num_tasks=10, temp=0.07, head="mlp", buffer_tracker=False, error_analysis=True, seed=0,
-             trick=dict(TRICK))
-    p.update(case_params(cfg))
-    p.update(over)
-    params = SimpleNamespace(**p)
-    seed_all(cfg["seed"])
-    model = setup_architecture(params).cuda()
-    opt = setup_opt(params.optimizer, model, params.learning_rate, params.weight_decay)
-    return params, model, name_match.get_agent(params.agent)(model, opt, params)
-
-
-def _rng_get():
-    return torch.get_rng_state(), np.random.get_state()
-
-
-def _rng_set(st):
-    torch.set_rng_state(st[0])
-    np.random.set_state(st[1])
-
-
 @pytest.fixture(scope="module")
 def agent_run(cuda, tmp_path_factory):
     """ER on the engine through the three tasks of the recorded case's stream with error_analysis on.  After each task, from the same
@@ -320,7 +282,7 @@ def agent_run(cuda, tmp_path_factory):
     from ocl_amd import ops, error_analysis as EA
     from ocl_amd.data import setup_test_loader
     cfg = E.EA_CASE
-    params, model, agent = _build_agent(cfg)
+    params, model, _, agent = build_agent(cfg, test_batch=E.EA_TEST_BATCH, error_analysis=True)
     tasks, tests = make_stream(cfg)
     loaders = setup_test_loader(tests, params)
     launches, copies, items, seen, forwards = [], [], [], [], []

@@ -6,12 +6,15 @@ tests/test_cpu_ewc.py).
 The accumulate step is judged element by element against 2 x accumulate_bounds, the first-order fp32 round-off of its statements: the
 factor covers an fma in place of a separate product and sum (the same factor, for the same reason, as test_gpu_agem.FACTOR).  The
 moving average and the normalisation are judged bit for bit.  Observed values: profiles/ewc_parity.txt."""
+import functools
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
+from agent_harness import (TRICK, build_agent, dev as _dev, host as _host, bits as _bits, rng_get as _rng_get, rng_set as _rng_set,
+                           rng_equal as _rng_equal, flat as _flat, events as _events)
 from conftest import gold
 from oracle.synth import make_stream, seed_all, digest_state, digest_nbt
 from test_cpu_adam import make_grads
@@ -20,22 +23,10 @@ from ewc_ref import EWC_CASE, EWC_LOOPS_CASE, ema_f32, normalize_f32
 
 pytestmark = pytest.mark.gpu
 
+_build_agent = functools.partial(build_agent, extra=ewc_ref.ref_params)
+
 FACTOR = 2.0
 SIZES = [1, 3, 4, 5, 1003, 4099, 1094750, 1109240]      # the last two: the parameter counts of the two Reduced-ResNet18 models
-TRICK = {'labels_trick': False, 'kd_trick': False, 'separated_softmax': False, 'review_trick': False, 'ncm_trick': False,
-         'kd_trick_star': False}
-
-
-def _dev(a, cuda):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(cuda)
-
-
-def _host(t):
-    return t.detach().cpu().numpy()
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
 
 
 def _same_bits(t, a):
@@ -281,23 +272,6 @@ def test_ops_wrappers_check_their_arguments_and_reuse_their_workspace(cuda):
 
 # ---- 6. the agent ---------------------------------------------------------------------------------------------------------------------
 
-def _build_agent(cfg, **over):
-    from ocl_amd import name_match
-    from ocl_amd.setup_elements import setup_architecture, setup_opt
-    p = dict(agent="EWC", retrieve="random", update="random", data="cifar10", mem_size=50, eps_mem_batch=10, cuda=True, epoch=1,
-             batch=10, test_batch=128, verbose=False, optimizer="SGD", learning_rate=0.1, weight_decay=0, mem_iters=1, subsample=50, k=3,
-             aser_type="asvm", n_smp_cls=1.5, num_tasks=10, temp=0.07, head="mlp", buffer_tracker=False, error_analysis=False, seed=0,
-             trick=dict(TRICK))
-    p.update(ewc_ref.ref_params(cfg))
-    p.update(over)
-    params = SimpleNamespace(**p)
-    seed_all(cfg["seed"])
-    model = setup_architecture(params).cuda()
-    opt = setup_opt(params.optimizer, model, params.learning_rate, params.weight_decay)
-    agent = name_match.get_agent(params.agent)(model, opt, params)
-    return params, model, opt, agent
-
-
 def _record_ops(monkeypatch):
     """Wraps the three ops: per accumulate call its inputs as they were before and its outputs; per moving average and normalisation
     the number of accumulate calls made before it."""
@@ -411,27 +385,6 @@ def test_agent_hands_the_right_things_to_the_kernels_and_their_output_to_the_opt
 
 
 # ---- 7. co-simulation against EwcOracle ------------------------------------------------------------------------------------------------
-
-def _rng_get():
-    return torch.get_rng_state(), np.random.get_state()
-
-
-def _rng_set(st):
-    torch.set_rng_state(st[0])
-    np.random.set_state(st[1])
-
-
-def _rng_equal(a, b):
-    return torch.equal(a[0], b[0]) and all(np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y for x, y in zip(a[1], b[1]))
-
-
-def _flat(state, names):
-    return torch.cat([state[k].detach().reshape(-1) for k in names]).double().numpy()
-
-
-def _events(ev, tag):
-    return [e for t, e in ev if t == tag]
-
 
 def _l1_rel(got, want):
     want = np.asarray(want, dtype=np.float64)

@@ -4,6 +4,7 @@ and the restatement of the reference's agent (tests/gdumb_ref.py, both pinned on
 
 The kernel is judged element by element against 1 x clip_bound, the first-order fp32 round-off of the clip (one half-ulp for the
 coefficient rounded to float, one for the product, plus the double accumulation).  Observed values: profiles/gdumb_parity.txt."""
+import functools
 import gc
 import random
 import weakref
@@ -13,29 +14,21 @@ import numpy as np
 import pytest
 import torch
 
+from agent_harness import (build_agent, make_params, dev as _dev, host as _host, bits as _bits, rng_get, rng_set as _rng_set,
+                           rng_equal as _rng_equal, flat as _flat, events as _events)
 from conftest import gold
-from oracle.synth import make_stream, seed_all, digest_state, case_params
+from oracle.synth import make_stream, seed_all, digest_state
 from test_cpu_adam import make_grads
 import gdumb_ref
 from gdumb_ref import ref_clip, worst_ratio, max_norm_for, GDUMB_CASE, BALANCER_CASES
 
 pytestmark = pytest.mark.gpu
 
+_rng_get = functools.partial(rng_get, python=True)      # the balancer draws from Python's `random`
+_params = functools.partial(make_params, extra=gdumb_ref.gdumb_params)
+_build_agent = functools.partial(build_agent, extra=gdumb_ref.gdumb_params)
+
 SIZES = [1, 3, 4, 5, 1003, 4099, 1094750, 1109240]
-TRICK = {'labels_trick': False, 'kd_trick': False, 'separated_softmax': False, 'review_trick': False, 'ncm_trick': False,
-         'kd_trick_star': False}
-
-
-def _dev(a, cuda):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(cuda)
-
-
-def _host(t):
-    return t.detach().cpu().numpy()
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
 
 
 # ---- 1. the kernel against ref_clip ---------------------------------------------------------------------------------------------------
@@ -207,28 +200,6 @@ def test_memory_follows_the_recorded_reference_update_with_one_scatter_per_batch
 
 # ---- 5. the agent -----------------------------------------------------------------------------------------------------------------------
 
-def _params(cfg, **over):
-    p = dict(agent="GDUMB", retrieve="random", update="random", data="cifar10", mem_size=50, eps_mem_batch=10, cuda=True, epoch=1,
-             batch=10, test_batch=128, verbose=False, optimizer="SGD", learning_rate=0.1, weight_decay=0, mem_iters=1, subsample=50, k=3,
-             aser_type="asvm", n_smp_cls=1.5, num_tasks=10, temp=0.07, head="mlp", buffer_tracker=False, error_analysis=False, seed=0,
-             trick=dict(TRICK))
-    p.update(case_params(cfg))
-    p.update(gdumb_ref.gdumb_params(cfg))
-    p.update(over)
-    return SimpleNamespace(**p)
-
-
-def _build_agent(cfg, **over):
-    from ocl_amd import name_match
-    from ocl_amd.setup_elements import setup_architecture, setup_opt
-    params = _params(cfg, **over)
-    seed_all(cfg["seed"])
-    model = setup_architecture(params).cuda()
-    opt = setup_opt(params.optimizer, model, params.learning_rate, params.weight_decay)
-    agent = name_match.get_agent(params.agent)(model, opt, params)
-    return params, model, opt, agent
-
-
 def _record_clips(monkeypatch):
     """Wraps ops.clip_grad_norm_: per call the array it was given, its contents before and after, and the info words."""
     from ocl_amd import ops
@@ -310,29 +281,6 @@ def test_a_run_of_several_tasks_does_not_accumulate_networks(cuda):
 
 
 # ---- 6. co-simulation against GdumbOracle -----------------------------------------------------------------------------------------------
-
-def _rng_get():
-    return torch.get_rng_state(), np.random.get_state(), random.getstate()
-
-
-def _rng_set(st):
-    torch.set_rng_state(st[0])
-    np.random.set_state(st[1])
-    random.setstate(st[2])
-
-
-def _rng_equal(a, b):
-    return (torch.equal(a[0], b[0]) and all(np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y for x, y in zip(a[1], b[1]))
-            and a[2] == b[2])
-
-
-def _flat(state, names):
-    return torch.cat([state[k].detach().reshape(-1) for k in names]).double().numpy()
-
-
-def _events(ev, tag):
-    return [e for t, e in ev if t == tag]
-
 
 def test_cosim_gdumb(cuda):
     """The three tasks of gdumb_c10, one train_learner call per task on both sides from the same host RNG state; before every memory

@@ -6,6 +6,7 @@ The kernel is judged by parity_bounds.check_vs_torch32, the project's rule for t
 most max(4 x the error of torch's own float32 statements on the same inputs, 4 ulp of the largest reference element), for each of the
 three losses and for the gradient.  Observed values: profiles/icarl_parity.txt (written by this module's report when PARITY_REPORT_DIR
 names a directory)."""
+import functools
 import os
 from types import SimpleNamespace
 
@@ -13,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+from agent_harness import (build_agent, dev as _dev, host as _host, bits as _bits, rng_get as _rng_get, rng_set as _rng_set,
+                           rng_equal as _rng_equal, flat as _flat, events as _events)
 from conftest import gold
 from guarded import Guarded
 from oracle.synth import make_stream, seed_all, digest_state
@@ -21,6 +24,8 @@ import icarl_ref
 from icarl_ref import ICARL_CASE, ref_bce_distill, torch32_bce_distill, logits_for
 
 pytestmark = pytest.mark.gpu
+
+_build_agent = functools.partial(build_agent, extra=icarl_ref.ref_params)
 
 REPORT = []
 # (n, n_stream, c, n_cls, n_old)
@@ -35,8 +40,6 @@ SHAPES = [
     (10, 10, 100, 10, 0),                                             # first task, no teacher
 ]
 SCALES = [1, 30, 300]
-TRICK = {'labels_trick': False, 'kd_trick': False, 'separated_softmax': False, 'review_trick': False, 'ncm_trick': False,
-         'kd_trick_star': False}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -50,18 +53,6 @@ def _parity_report():
             for case, tensor, err, e_ref, bound, ratio in REPORT:
                 f.write("%-52s %-8s %-12.4g %-12s %-12.4g %.3f\n" % (case, tensor, err, e_ref, bound, ratio))
             f.write("worst err/bound %.3f over %d rows\n" % (max(r[5] for r in REPORT), len(REPORT)))
-
-
-def _dev(a, cuda, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(cuda)
-
-
-def _host(t):
-    return t.detach().cpu().numpy()
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
 
 
 def _case(n, n_stream, c, n_cls, n_old, scale):
@@ -228,23 +219,6 @@ def test_bad_arguments_are_refused_and_nothing_is_written(cuda):
 
 # ---- 4. the agent ---------------------------------------------------------------------------------------------------------------------
 
-def _build_agent(cfg, **over):
-    from ocl_amd import name_match
-    from ocl_amd.setup_elements import setup_architecture, setup_opt
-    p = dict(agent="ICARL", retrieve="random", update="random", data="cifar10", mem_size=50, eps_mem_batch=10, cuda=True, epoch=1,
-             batch=10, test_batch=128, verbose=False, optimizer="SGD", learning_rate=0.1, weight_decay=0, mem_iters=1, subsample=50, k=3,
-             aser_type="asvm", n_smp_cls=1.5, num_tasks=10, temp=0.07, head="mlp", buffer_tracker=False, error_analysis=False, seed=0,
-             trick=dict(TRICK))
-    p.update(icarl_ref.ref_params(cfg))
-    p.update(over)
-    params = SimpleNamespace(**p)
-    seed_all(cfg["seed"])
-    model = setup_architecture(params).cuda()
-    opt = setup_opt(params.optimizer, model, params.learning_rate, params.weight_decay)
-    agent = name_match.get_agent(params.agent)(model, opt, params)
-    return params, model, opt, agent
-
-
 def _spy_bce(patch):
     """Records every ops.bce_distill call; `patch(obj, name, value)` is monkeypatch.setattr or a stand-in for it."""
     from ocl_amd import ops
@@ -367,27 +341,6 @@ def test_agent_hands_the_right_things_to_the_kernel_and_its_gradient_to_the_back
 
 
 # ---- 5. co-simulation against IcarlOracle ----------------------------------------------------------------------------------------------
-
-def _rng_get():
-    return torch.get_rng_state(), np.random.get_state()
-
-
-def _rng_set(st):
-    torch.set_rng_state(st[0])
-    np.random.set_state(st[1])
-
-
-def _rng_equal(a, b):
-    return torch.equal(a[0], b[0]) and all(np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y for x, y in zip(a[1], b[1]))
-
-
-def _flat(state, names):
-    return torch.cat([state[k].detach().reshape(-1) for k in names]).double().cpu().numpy()
-
-
-def _events(ev, tag):
-    return [e for t, e in ev if t == tag]
-
 
 def test_cosim_icarl(cuda, monkeypatch):
     """The three tasks of the case, one train_learner call (six batches) per task; before every call the HIP model is loaded with the

@@ -5,12 +5,15 @@ reference's loop (tests/lwf_ref.py, all pinned on the CPU by tests/test_cpu_lwf.
 The kernel is judged by parity_bounds.check_vs_torch32, the project's rule for transcendental kernels: its error against float64 is at
 most max(4 x the error of torch's own float32 statements on the same inputs, 4 ulp of the largest reference element), for each of the
 three losses and for the gradient.  Observed values: profiles/lwf_parity.txt."""
+import functools
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
+from agent_harness import (TRICK, build_agent, dev as _dev, host as _host, bits as _bits, rng_get as _rng_get, rng_set as _rng_set,
+                           rng_equal as _rng_equal, flat as _flat, events as _events)
 from conftest import gold
 from guarded import Guarded
 from oracle.synth import make_stream, seed_all, digest_state
@@ -20,6 +23,8 @@ from lwf_ref import LWF_CASE, ref_blend, torch32_blend, logits_for
 
 pytestmark = pytest.mark.gpu
 
+_build_agent = functools.partial(build_agent, extra=lwf_ref.ref_params)
+
 REPORT = []
 # (n, c, logit scale, T): the CE family's shapes with the KD family's temperatures; they bracket 4 waves per block and 64 lanes per row
 CASES = [(1, 5, 1, 2.0), (3, 10, 30, 1.0), (4, 64, 1, 4.0), (5, 100, 300, 2.0), (10, 100, 1, 2.0), (10, 65, 1, 2.0), (10, 128, 30, 3.0),
@@ -27,20 +32,6 @@ CASES = [(1, 5, 1, 2.0), (3, 10, 30, 1.0), (4, 64, 1, 4.0), (5, 100, 300, 2.0), 
 # both sides of the row length at which the kernel stops holding the row in registers (256), and the last full register
 THRESHOLD_CASES = [(6, 192, 1, 2.0), (6, 193, 30, 3.0), (6, 256, 1, 2.0), (6, 257, 1, 2.0), (5, 321, 30, 3.0)]
 WEIGHTS = [(1 / 2, 1 / 2), (1 / 3, 2 / 3), (1 / 10, 9 / 10)]
-TRICK = {'labels_trick': False, 'kd_trick': False, 'separated_softmax': False, 'review_trick': False, 'ncm_trick': False,
-         'kd_trick_star': False}
-
-
-def _dev(a, cuda, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(cuda)
-
-
-def _host(t):
-    return t.detach().cpu().numpy()
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
 
 
 def _case(n, c, scale, T):
@@ -187,23 +178,6 @@ def test_bad_arguments_are_refused_and_nothing_is_written(cuda):
 
 # ---- 4. the agent ---------------------------------------------------------------------------------------------------------------------
 
-def _build_agent(cfg, **over):
-    from ocl_amd import name_match
-    from ocl_amd.setup_elements import setup_architecture, setup_opt
-    p = dict(agent="LWF", retrieve="random", update="random", data="cifar10", mem_size=50, eps_mem_batch=10, cuda=True, epoch=1,
-             batch=10, test_batch=128, verbose=False, optimizer="SGD", learning_rate=0.1, weight_decay=0, mem_iters=1, subsample=50, k=3,
-             aser_type="asvm", n_smp_cls=1.5, num_tasks=10, temp=0.07, head="mlp", buffer_tracker=False, error_analysis=False, seed=0,
-             trick=dict(TRICK))
-    p.update(lwf_ref.ref_params(cfg))
-    p.update(over)
-    params = SimpleNamespace(**p)
-    seed_all(cfg["seed"])
-    model = setup_architecture(params).cuda()
-    opt = setup_opt(params.optimizer, model, params.learning_rate, params.weight_decay)
-    agent = name_match.get_agent(params.agent)(model, opt, params)
-    return params, model, opt, agent
-
-
 def _spy_blend(monkeypatch):
     from ocl_amd import ops
     calls = []
@@ -307,27 +281,6 @@ def test_agent_hands_the_right_things_to_the_kernel_and_its_gradient_to_the_back
 
 
 # ---- 5. co-simulation against LwfOracle ------------------------------------------------------------------------------------------------
-
-def _rng_get():
-    return torch.get_rng_state(), np.random.get_state()
-
-
-def _rng_set(st):
-    torch.set_rng_state(st[0])
-    np.random.set_state(st[1])
-
-
-def _rng_equal(a, b):
-    return torch.equal(a[0], b[0]) and all(np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y for x, y in zip(a[1], b[1]))
-
-
-def _flat(state, names):
-    return torch.cat([state[k].detach().reshape(-1) for k in names]).double().cpu().numpy()
-
-
-def _events(ev, tag):
-    return [e for t, e in ev if t == tag]
-
 
 def test_cosim_lwf(cuda, monkeypatch):
     """The three tasks of lwf_c10 concatenated, 9 sequential slices of 20, one train_learner call (two batches) per slice; before every

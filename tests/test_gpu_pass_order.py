@@ -33,6 +33,7 @@ import torch
 
 import pass_order_cases as PC
 import test_gpu_net as TN
+from agent_harness import host as _host
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -111,10 +112,6 @@ def _forward_probe(m, model, probe):
 
 def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _host(t):
-    return t.detach().cpu().numpy()
 
 
 def isolated(model, probe):

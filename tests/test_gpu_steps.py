@@ -5,43 +5,23 @@
  (c) size-independent properties at BASELINE.json's full sizes (mem 5000 / 10000, eps_mem_batch 100, 84x84).
 """
 import copy
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
+import agent_harness as H
+from agent_harness import TRICK, make_params, rng_get as _rng_get, rng_set as _rng_set, rng_equal as _rng_equal, flat as _flat  # noqa: F401  (other test files import them from here)
 from conftest import gold
 from oracle import ocl_oracle as O
-from oracle.synth import STEP_CASES, make_stream, seed_all, digest_state, digest_nbt, digest_rng, case_params, class_images
+from oracle.synth import STEP_CASES, make_stream, seed_all, digest_state, digest_nbt, digest_rng, class_images
 
 pytestmark = pytest.mark.gpu
 
-TRICK = {'labels_trick': False, 'kd_trick': False, 'separated_softmax': False, 'review_trick': False, 'ncm_trick': False,
-         'kd_trick_star': False}
-
-
-def make_params(cfg, **over):
-    p = dict(agent="ER", retrieve="random", update="random", data="cifar100", mem_size=1000, eps_mem_batch=10, cuda=True, epoch=1,
-             batch=10, test_batch=128, verbose=False, optimizer="SGD", learning_rate=0.1, weight_decay=0, mem_iters=1, subsample=50, k=3,
-             aser_type="asvm", n_smp_cls=1.5, num_tasks=10, temp=0.07, head="mlp", buffer_tracker=False, error_analysis=False, seed=0,
-             trick=dict(TRICK))
-    p.update(case_params(cfg))
-    p.update(over)
-    return SimpleNamespace(**p)
-
 
 def build_agent(cfg, **over):
-    from ocl_amd import name_match
-    from ocl_amd.setup_elements import setup_architecture, setup_opt
-    from ocl_amd.utils import maybe_cuda
-    params = make_params(cfg, **over)
-    seed_all(cfg["seed"])
-    model = maybe_cuda(setup_architecture(params), params.cuda)
-    opt = setup_opt(params.optimizer, model, params.learning_rate, params.weight_decay)
-    agent = name_match.agents[params.agent](model, opt, params)
-    if params.agent == "SCR":
-        agent.transform = lambda x: x      # identity augmentation on both sides (kornia is unpinned)
+    """(params, model, agent): the shape this file, test_gpu_loops, test_gpu_parity2, test_gpu_f4 and test_gpu_datasets unpack."""
+    params, model, _, agent = H.build_agent(cfg, **over)
     return params, model, agent
 
 
@@ -86,23 +66,6 @@ def test_free_running_cases_vs_reference_golden(cuda, name):
 # ---------------------------------------------------------------------------------------------------------------------
 # co-simulation: HIP agent and CPU oracle agent stepped one iteration at a time from IDENTICAL state
 # ---------------------------------------------------------------------------------------------------------------------
-
-def _rng_get():
-    return torch.get_rng_state(), np.random.get_state()
-
-
-def _rng_set(st):
-    torch.set_rng_state(st[0])
-    np.random.set_state(st[1])
-
-
-def _rng_equal(a, b):
-    return torch.equal(a[0], b[0]) and all(np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y for x, y in zip(a[1], b[1]))
-
-
-def _flat(state, names):
-    return torch.cat([state[k].detach().reshape(-1) for k in names]).double().numpy()
-
 
 def _oracle_self_distance(oa, x, y, st, w0, dw_o):
     """The oracle's own sensitivity for one call: the same call from a copy of the oracle whose weights are moved by one unit in the

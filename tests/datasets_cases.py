@@ -1,6 +1,7 @@
 """Shared by tests/test_gpu_datasets.py and tests/test_cpu_datasets.py (a plain helper module, not a conftest): the pass grid of the 50 x 50
-(openloris) and 128 x 128 (core50) inputs, and the single-layer parity cases for the kernel forms the planner gives there that the
-32 / 84 grid of tests/layer_forms.py does not contain."""
+(openloris) and 128 x 128 (core50) inputs, and the single-layer parity cases for the kernel forms the planner gives there that
+layer_forms.COVERED does not contain.  (The dense grid of tests/layer_forms.py covers these input sizes too, up to the default max_batch;
+a form it finds is accepted with a case in either table, and its edge sizes are in layer_forms.EDGE_CASES.)"""
 import layer_forms as LF
 
 HW = (50, 128)

@@ -1,7 +1,9 @@
-"""CPU: every kernel form the network engine plans (ocl_test_net_forms: the very function the engine's plan cache calls) over a grid of
-passes that crosses every planner threshold -- 32 x 32 and 84 x 84, train passes of 1 - 64, 100, 110, 128, 160, 220, 256 and 300 images
-in one and two BatchNorm groups, eval passes as the engine plans them up to 416 images -- must have a single-layer parity case in
-tests/test_gpu_layers.py (layer_forms.COVERED).  A planner change that reaches a new form without a parity case fails here."""
+"""CPU: every kernel form the network engine plans (ocl_test_net_forms: the very function the engine's plan cache calls) over the dense
+grid of layer_forms.pass_grid -- 32 x 32, 50 x 50, 84 x 84 and 128 x 128, every train pass of 1 .. resnet._default_max_batch images in
+one and two BatchNorm groups, every eval pass the engine's rounding can plan, and the passes above the defaults (300 train images, eval
+passes up to 416 at 32 x 32 and 84 x 84) -- must have a single-layer parity case in tests/test_gpu_layers.py (layer_forms.COVERED) or
+tests/test_gpu_datasets.py (datasets_cases.NEW_FORMS).  A planner change that reaches a new form without a parity case fails here; the
+grid itself and the edge sizes of every form (layer_forms.EDGE_CASES) are checked in tests/test_cpu_form_grid.py."""
 import ctypes as C
 
 import pytest
@@ -17,14 +19,13 @@ def lib():
 
 
 def test_every_planned_form_has_a_parity_case(lib):
+    import datasets_cases as DC
     forms = LF.enumerate_forms(lib)
-    missing = sorted(set(forms) - set(LF.COVERED))
-    assert not missing, "forms without a case in layer_forms.COVERED: %s" % missing
+    missing = sorted(set(forms) - set(LF.COVERED) - set(DC.NEW_FORMS))
+    assert not missing, "forms without a case in layer_forms.COVERED / datasets_cases.NEW_FORMS: %s" % missing
     assert len(forms) >= 100
     # every case still reaches its form where the list says
-    stale = [k for k, (hw, n, g, layer, dr) in LF.COVERED.items()
-             if not any(kk == k and e.layer == layer and e.dir == dr
-                        for kk, e in LF.net_forms(lib, hw, n, g, 0 if k.endswith("/affine") else 1))]
+    stale = [k for k, case in LF.COVERED.items() if not LF.plans(lib, k, case)]
     assert not stale, stale
 
 
@@ -71,7 +72,9 @@ def test_tier1_integer_cases_stay_below_2_24(lib):
     """Tier 1 draws inputs, weights and gradients from {-2..2}: every partial sum of a case is bounded by (terms) * 4, which must stay below
     2^24 for the fp32 result to be exact in any summation order."""
     worst = 0
-    for k, (hw, n, g, layer, dr) in LF.COVERED.items():
+    cases = list(LF.COVERED.items()) + [(k, case) for k, _, case in LF.EDGE_LIST]
+    assert len(cases) > len(LF.COVERED) + 300
+    for k, (hw, n, g, layer, dr) in cases:
         for kk, e in LF.net_forms(lib, hw, n, g, 0 if k.endswith("/affine") else 1):
             if kk != k or e.layer != layer or e.dir != dr:
                 continue
@@ -87,4 +90,5 @@ def test_tier1_integer_cases_stay_below_2_24(lib):
             worst = max(worst, _max_partial(terms) + 8)
     # the fixed shapes of test_gpu_layers.py: 220-view pass wgrad of the stem (220 * 32 * 32 terms), 84 x 84 at 3 images
     worst = max(worst, _max_partial(220 * 32 * 32), _max_partial(3 * 84 * 84))
-    assert worst < 2 ** 24, worst
+    # (the edge cases' worst are the stride-1 weight gradients over whole inputs: 128 images of 128 x 128 and 300 of 84 x 84, 8.4e6 and 8.5e6)
+    assert 128 * 128 * 128 * 4 <= worst < 2 ** 24, worst

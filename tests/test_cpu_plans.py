@@ -82,7 +82,10 @@ def test_every_layer_gets_a_plan_that_fits(n, groups, hw):
 
 
 @pytest.mark.parametrize("n,groups,hw", [(1, 1, 32), (7, 1, 32), (10, 1, 32), (20, 2, 32), (50, 2, 32), (100, 1, 32), (150, 2, 32), (220, 2, 32), (272, 1, 32),
-                                         (410, 1, 32), (1, 1, 84), (6, 1, 84), (15, 1, 84), (20, 2, 84), (50, 1, 84), (60, 1, 84), (220, 2, 84)])
+                                         (410, 1, 32), (1, 1, 84), (6, 1, 84), (15, 1, 84), (20, 2, 84), (50, 1, 84), (60, 1, 84), (220, 2, 84),
+                                         # the boundaries of the forms the dense grid of tests/layer_forms.py added, up to the default max_batch
+                                         (67, 1, 32), (70, 2, 32), (341, 1, 32), (396, 2, 32), (512, 1, 32), (512, 2, 32),
+                                         (27, 1, 50), (199, 1, 50), (256, 2, 50), (256, 2, 84), (23, 1, 128), (65, 1, 128), (128, 2, 128)])
 def test_every_plan_covers_its_output_exactly_once(n, groups, hw):
     """`kbench ... cover` replays every plan's tables on the host (the lane -> pixel maps of conv_t_kernel / conv_q_kernel /
     conv_s_kernel, aligned and per-tile): every lattice pixel written exactly once, operand reads and patch units inside the patch,

@@ -6,7 +6,8 @@ like an fmaf chain, no reduced-precision path), so with small-integer inputs, we
 every form's result is exact whatever its tiling and summation order.  Outputs and weight gradients are compared for BIT equality with
 the float64 reference: a dropped, doubled or misplaced product, tile, tap or channel quad is an O(1) error.  One case per form in
 layer_forms.COVERED (the cheapest pass / layer the planner gives it at; tests/test_cpu_forms.py checks that list against the planner);
-each case asserts that the hook ran the form it names.  Sentinel inputs (non-zero only in the last image, the last pixel, the border,
+each case asserts that the hook ran the form it names.  The same case bodies run every form at its edge sizes -- most images, odd
+images per group, the other lattices -- in tests/test_gpu_form_grid.py.  Sentinel inputs (non-zero only in the last image, the last pixel, the border,
 the last channel quad) make a dropped tile visible even where the rest of the tensor would hide it.
 
 Tier 2 (random fp32): |got - ref| <= 1.01 * K * 2^-24 * sum|x * w| per element (a bound an exact-fp32 kernel cannot exceed), and the
@@ -308,6 +309,11 @@ def _conv_form_is_exact(lib, key, det):
 
 @pytest.mark.parametrize("key", LF.WGRAD_KEYS)
 def test_wgrad_form_is_exact(lib, key):
+    _wgrad_form_is_exact(lib, key, ".m" in key)
+
+
+def _wgrad_form_is_exact(lib, key, merged):
+    """merged: through conv_wgrad_multi_kernel (a '.m' key's own launch), or the layer's plan as a launch of its own."""
     e = find_entry(lib, key)
     d = e.wdesc
     g = torch.Generator().manual_seed(zlib.crc32(key.encode()) % 10007)
@@ -317,7 +323,6 @@ def test_wgrad_form_is_exact(lib, key):
         x[..., 3] = 0
     dy = ints((d.n, ho, wo, d.cout), g)
     ref = ref_wgrad(x, dy, d)
-    merged = ".m" in key
     xf_ops = None
     if key.endswith("/xf"):   # transform with gamma 1, beta 0, mean 0, invstd 1: relu(x) staged, still exact
         G = d.xf_groups
@@ -326,8 +331,8 @@ def test_wgrad_form_is_exact(lib, key):
     acc = sum(map(ord, key)) % 2
     grad0 = [ints(ref.shape, g)] if acc else None
     got, forms = run_wgrad(lib, [d], [x], [dy], multi=1 if merged else 0, accumulate=acc, grad0=grad0, xf_ops=xf_ops)
-    k = LF.wgrad_key(forms[0], xf_ops is not None, merged)
-    print("FORM", key, "ran", k, "n=%d layer=%d accumulate=%d" % (d.n, e.layer, acc))
+    k = LF.wgrad_key(forms[0], xf_ops is not None, ".m" in key)
+    print("FORM", key, "ran", k, "n=%d layer=%d accumulate=%d merged=%d" % (d.n, e.layer, acc, merged))
     assert k == key
     assert_exact(got[0], ref + (grad0[0] if acc else 0), key)
 
@@ -485,7 +490,15 @@ def _bound_check(got, ref64, mag, K, cpu32, what):
     assert rms <= 4 * rms32 + 1e-30, "%s: RMS error %g vs fp32 CPU %g" % (what, rms, rms32)
 
 
-@pytest.mark.parametrize("key", [k for k in CONV_KEYS if k.endswith("/plain") or k.endswith("/stats")][::3] + ["wg3x2.pf8/plain", "wgq3.pf8/plain"])
+# (every third /plain and /stats key of the grid before it became dense, and one key of each family the dense grid added)
+TIER2_KEYS = ['q1.pf12/plain', 'q2.pf12/stats', 's1/stats', 't1x1.res.c1.pf4/plain', 't1x1.res.c1.pf8/stats', 't1x1.ring.c1.pf4/stats',
+              't1x1.ring.c4.pf4/plain', 't1x1.two.c4.pf8/plain', 't2x1.res.c1.pf8/plain', 't2x1.res.c4.pf8/plain', 't2x1.ring.c1.pf8/stats',
+              't2x2.two.c1.pf8/plain', 't3x1.ring.c1.pf4/stats', 't3x1.ring.c4.pf8/plain', 't3x2.two.c1.pf8/stats', 't5x1.ring.c1.pf8/stats',
+              't5x2.two.c1.pf8/plain', 'wx1x1/stats', 't2x1.two.c4.pf8/plain', 't4x1.two.c1.pf8/stats', 't5x1.res.c1.pf8/plain',
+              "wg3x2.pf8/plain", "wgq3.pf8/plain", "wg1x2.pf8/plain"]
+
+
+@pytest.mark.parametrize("key", TIER2_KEYS)
 def test_random_fp32_within_the_exact_fp32_bound(lib, key):
     e = find_entry(lib, key)
     g = torch.Generator().manual_seed(7)
@@ -533,6 +546,11 @@ def _bn_ref(y, groups, gamma, beta, eps=1e-5):
 def test_input_transform_against_float64_batchnorm(lib, key, det):
     """conv2 of a block applies bn1 + ReLU of conv1's raw output while staging, from conv1's batch sums (EPI_STATS cells), and writes
     bn1's saved statistics and running statistics on the way."""
+    _input_transform_against_float64_batchnorm(lib, key, det)
+
+
+def _input_transform_against_float64_batchnorm(lib, key, det):
+    """Returns the worst error / bound over the outputs that are held to the bound (for the parity reports)."""
     e = find_entry(lib, key)
     d = e.desc
     lib.ocl_set_deterministic(det)
@@ -575,6 +593,7 @@ def test_input_transform_against_float64_batchnorm(lib, key, det):
         bad = (err > lim) & ~hit
         assert not bool(bad.any()), "%s: %d outputs off (worst %g)" % (key, int(bad.sum()), float((err - lim)[bad].max()))
         check_stats(cell_totals(stats, G, d.cout, det), stats_ref(got, G), stats_ref(got.abs(), G), key)
+        return float((err / lim.clamp(min=1e-300))[~hit].max())
     finally:
         lib.ocl_set_deterministic(0)
 

@@ -65,6 +65,11 @@ CASES = [
     ("SCR", "cifar100", "None", 8, 2),          # SupConResNet(head='None'): normalised features, out_dim = feature_dim
     ("SCR", "mini_imagenet", "mlp", 4, 2),      # the 640-wide MLP head; the 11 x 11 final map cropped to 8 x 8 by avg_pool2d(4)
     ("SCR", "cifar100", "linear", 36, 2),
+    # passes whose forms tests/layer_forms.py's dense grid found unpinned: a single-layer hook cannot see a form's hand-over to the BatchNorm
+    # and weight-gradient kernels around it (the statistics cells, the saved dL/dy)
+    ("ER", "cifar100", None, 67, 1),        # layer 1's weight gradient on wg1x2.pf8 (65 .. 71 images): ER, batch 10 + 57 memory images
+    ("SCR", "cifar100", "mlp", 70, 2),      # the same with the input transform: SCR with eps_mem_batch 25
+    ("ER", "cifar100", None, 342, 1),       # layer 4's shortcut on t4x1.two.c1.pf8/stats, its merged data gradient on t2x1.two.c4.pf8
 ]
 
 BLOCKS = ["layer%d.%d" % (l, b) for l in range(1, 5) for b in range(2)]

@@ -31,6 +31,7 @@ struct BnInfo {
     int gamma_t, beta_t;  // tensor indices
     int64_t stat_off;     // into the running flat array: mean[C], var[C]
     int64_t arena_off;    // into per-BN arenas of size kGmax*2*C (doubles) / 2*C floats for the fold
+    int64_t barena_off;   // the backward's reduction arena: 2*kGmax*2*C cells, two BatchNorms sharing dz ([set][G][2][C]) at every G <= kGmax
     int64_t fused_off;    // one-pass BatchNorm backward: replicated accumulators + arrival counter (doubles, in the bsums arena)
     int64_t save_off;     // into the slot's saved mean/invstd area (floats): mean[kGmax*C], invstd[kGmax*C]
 };
@@ -344,8 +345,12 @@ static int build_layout(ocl_net* n) {
     n->stats_doubles = so * kStatReps;   // kStatReps replicas of the whole arena, replica stride `so`
     n->stats_rep_stride = so;
     n->off_stats = takeb(n->stats_doubles * (int64_t)sizeof(StatCell));   // (counts are in accumulator cells)
-    // backward: [G][2][C] per BN as well, followed by the one-pass kernel's arenas (8 replicas x 2 groups x 2 x C + counter per BN)
-    int64_t fo = so;
+    // backward: [2 sets][G][2][C] per BN, followed by the one-pass kernel's arenas (8 replicas x 2 groups x 2 x C + counter per BN)
+    int64_t fo = 0;
+    for (auto& b : n->bns) {
+        b.barena_off = fo;
+        fo += (int64_t)2 * kGmax * 2 * b.C;
+    }
     for (auto& b : n->bns) {
         b.fused_off = fo;
         fo += (int64_t)8 * 2 * 2 * b.C + 8;   // + 9 arrival counters (unsigned)
@@ -1266,17 +1271,13 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
             a.dgamma[k] = GT(b.gamma_t);
             a.dbeta[k] = GT(b.beta_t);
         }
-        // sums are addressed [set][G][2][C] inside conv_a's arena of kGmax*2*C doubles: two sets need 2*G <= kGmax
-        a.sums = bsums + n->bns[ca.bn].arena_off;
+        // sums are addressed [set][G][2][C] inside conv_a's arena of 2*kGmax*2*C cells: two sets fit at every G <= kGmax
+        a.sums = bsums + n->bns[ca.bn].barena_off;
         // one-pass kernel (<= 2 groups; two BatchNorms sharing dz each bring their own accumulator arena)
         if (G <= 2) {
             a.fsums = bsums + n->bns[ca.bn].fused_off;
             a.barrier = (unsigned*)(a.fsums + (int64_t)8 * 2 * 2 * ca.Cout);
             if (conv_b >= 0) a.fsums_b = bsums + n->bns[n->convs[conv_b].bn].fused_off;
-        }
-        if (conv_b >= 0 && 2 * G > kGmax) {
-            set_error("bn_bwd: groups=%d too large for a shared reduction arena", G);
-            return OCL_ERR_ARG;
         }
         a.accumulate = accumulate;
         a.frozen = frozen ? 1 : 0;

@@ -70,14 +70,14 @@ def producer_inputs(dims, groups, seed, act=None):
     rng = np.random.default_rng(seed)
     cc = const_channel(cin)
     if act is None:
-        assert n % groups == 0 and groups in (1, 2)
+        assert n % groups == 0 and groups in (1, 2, 3)
         per = n // groups
         x = rng.standard_normal((per, hin, win, cin_t)).astype(np.float32).astype(np.float64)
         x[..., cc] = 1.0
         if cin == 3:
             x[..., 3] = 0.0
-        if groups == 2:
-            x = np.concatenate([x, -x], axis=0)
+        if groups > 1:      # (a third group holds the images of group 0 again: every neighbour of a group is its mirror image)
+            x = np.concatenate([x if g % 2 == 0 else -x for g in range(groups)], axis=0)
     else:
         x = np.asarray(act, np.float64)
     w = rng.standard_normal((cout, cin, k, k))
@@ -143,9 +143,10 @@ CONSUMERS = [
 ]
 
 # (b) the convolution's input transform as a consumer of exact cells: (n, hw, C, groups, the family the planner gives a C -> C 3x3 convolution of
-# this pass; the GPU test asserts it): conv_t, conv_s and conv_q, each at one or two groups
+# this pass; the GPU test asserts it): conv_t, conv_s and conv_q, each at one or two groups, and conv_t at three (the third row of the
+# [groups][Cin/4][2][4] table and of the saved statistics, the third running update)
 # (conv_q takes a C -> C convolution only from 64 images of 32 x 32 on: above the n <= 12 of the other consumer cases)
-XF_CONSUMERS = [(10, 32, 20, 2, "t"), (6, 16, 40, 1, "t"), (12, 8, 160, 2, "s"), (5, 4, 80, 1, "s"), (64, 32, 20, 2, "q")]
+XF_CONSUMERS = [(10, 32, 20, 2, "t"), (6, 16, 40, 1, "t"), (12, 8, 160, 2, "s"), (5, 4, 80, 1, "s"), (64, 32, 20, 2, "q"), (6, 16, 40, 3, "t")]
 
 # (c) the ladder cases of the six places: (n, hw, C, groups); every group holds at least 129 pixels
 LADDERS = [(4, 16, 40, 1), (4, 16, 20, 2)]

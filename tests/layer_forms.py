@@ -583,6 +583,177 @@ EDGE_CASES = {
 }
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# passes of three to eight BatchNorm groups
+# ---------------------------------------------------------------------------------------------------------------------------------
+# model.forward_views hands len(views) to the engine as the group count and ocl_net_forward takes up to eight.  GROUPS, COVERED and EDGE_CASES
+# above stay the one- and two-group grid; this is a second sweep beside it.
+MANY_GROUPS = (3, 4, 5, 6, 7, 8)
+GROUP_EPILOGUES = ("/stats", "/stats_xf", "/xf")     # the forms whose epilogue or staging reads a tile's group
+
+
+def group_grid():
+    """(hw, n, groups, 1) of every train pass of g .. max_batch(hw) images in g = 3 .. 8 equal BatchNorm groups."""
+    for hw in HW:
+        mb = max_batch(hw)
+        for n in range(1, mb + 1):
+            for g in MANY_GROUPS:
+                if n >= g and n % g == 0:
+                    yield hw, n, g, 1
+
+
+def group_sweep(lib):
+    """sweep() over group_grid()."""
+    if "groups" not in _SWEEP:
+        out = {}
+        for hw, n, g, train in group_grid():
+            arr, cnt = _net_entries(lib, hw, n, g, train)
+            for i in range(cnt):
+                e = arr[i]
+                k = (e.desc if e.dir < 2 else e.wdesc).k
+                out.setdefault(_entry_key(e, train), []).append((hw, n, g, e.layer, e.dir, entry_cost(hw, n, e), k))
+        _SWEEP["groups"] = out
+    return _SWEEP["groups"]
+
+
+def group_cases(lib):
+    """{key: [(kind, hw, n, groups, layer, direction)]} by the rule above GROUP_CASES."""
+    out = {}
+    for key, rows in sorted(group_sweep(lib).items()):
+        gmax = max(r[2] for r in rows)
+        picked = [("most", _cheapest([r for r in rows if r[2] == gmax])[:5])]
+        if key.endswith(GROUP_EPILOGUES):
+            c = _cheapest(rows)[:5]
+            if c != picked[0][1]:
+                picked.append(("cheapest", c))
+        out[key] = [(kind,) + c for kind, c in picked]
+    return out
+
+
+# The many-group cases of every form a pass of 3 .. 8 BatchNorm groups plans: key -> [(kind, hw, n, groups, layer index, direction)], generated
+# by group_cases() from group_grid() (regenerate with `python tests/layer_forms.py groups`; tests/test_cpu_form_grid.py re-derives the table
+# from the planner).  Of all the entries of that grid that plan a key:
+#   most      the cheapest (entry_cost) among those with the most groups -- the most group boundaries inside a workgroup's tile range, the
+#             highest index into the per-group tables;
+#   cheapest  for the forms whose epilogue or staging reads the group (GROUP_EPILOGUES), the cheapest of all when it is another one -- the
+#             fewest images per group the form is planned at.
+# Being the cheapest with its property, no case can be replaced by a cheaper one; the bounds of ref_work are those of EDGE_CASES.
+GROUP_CASES = {
+    'q1.pf12/plain': [('most', 50, 16, 8, 1, 1)],
+    'q1.pf12/stats': [('most', 50, 16, 8, 1, 0), ('cheapest', 50, 14, 7, 1, 0)],
+    'q1.pf12/stats_xf': [('most', 50, 16, 8, 2, 0), ('cheapest', 50, 14, 7, 2, 0)],
+    'q2.pf12/plain': [('most', 32, 64, 8, 1, 1)],
+    'q2.pf12/stats': [('most', 32, 64, 8, 1, 0), ('cheapest', 32, 64, 4, 1, 0)],
+    'q2.pf12/stats_xf': [('most', 32, 64, 8, 2, 0), ('cheapest', 32, 64, 4, 2, 0)],
+    'q2.pf4/stats': [('most', 32, 64, 8, 0, 0), ('cheapest', 128, 4, 4, 0, 0)],
+    's1/plain': [('most', 32, 8, 8, 11, 1)],
+    's1/stats': [('most', 32, 8, 8, 13, 0), ('cheapest', 32, 3, 3, 13, 0)],
+    's1/stats_xf': [('most', 32, 8, 8, 11, 0), ('cheapest', 32, 3, 3, 11, 0)],
+    's2/plain': [('most', 32, 40, 8, 11, 1)],
+    's2/stats': [('most', 32, 40, 8, 13, 0), ('cheapest', 50, 15, 3, 13, 0)],
+    's2/stats_xf': [('most', 32, 40, 8, 11, 0), ('cheapest', 50, 15, 3, 11, 0)],
+    't1x1.res.c1.pf4/plain': [('most', 32, 8, 8, 1, 1)],
+    't1x1.res.c1.pf4/stats': [('most', 32, 8, 8, 0, 0), ('cheapest', 32, 3, 3, 0, 0)],
+    't1x1.res.c1.pf4/stats_xf': [('most', 32, 8, 8, 2, 0), ('cheapest', 32, 3, 3, 2, 0)],
+    't1x1.res.c1.pf8/plain': [('most', 32, 8, 8, 6, 1)],
+    't1x1.res.c1.pf8/stats': [('most', 32, 8, 8, 8, 0), ('cheapest', 32, 3, 3, 8, 0)],
+    't1x1.res.c1.pf8/stats_xf': [('most', 32, 8, 8, 6, 0), ('cheapest', 32, 3, 3, 6, 0)],
+    't1x1.res.c4.pf4/plain': [('most', 32, 8, 8, 5, 1)],
+    't1x1.res.c4.pf8/plain': [('most', 32, 8, 8, 10, 1)],
+    't1x1.ring.c1.pf4/stats': [('most', 50, 8, 8, 5, 0), ('cheapest', 50, 3, 3, 5, 0)],
+    't1x1.ring.c1.pf8/plain': [('most', 32, 8, 8, 17, 1)],
+    't1x1.ring.c1.pf8/stats': [('most', 32, 8, 8, 10, 0), ('cheapest', 32, 3, 3, 10, 0)],
+    't1x1.ring.c1.pf8/stats_xf': [('most', 84, 3, 3, 6, 0)],
+    't1x1.ring.c4.pf8/plain': [('most', 32, 8, 8, 15, 1)],
+    't1x1.two.c1.pf8/stats': [('most', 84, 8, 8, 10, 0), ('cheapest', 84, 8, 4, 10, 0)],
+    't1x1.two.c4.pf8/plain': [('most', 32, 208, 8, 15, 1)],
+    't2x1.res.c1.pf4/plain': [('most', 32, 16, 8, 1, 1)],
+    't2x1.res.c1.pf4/stats': [('most', 32, 16, 8, 0, 0), ('cheapest', 50, 5, 5, 0, 0)],
+    't2x1.res.c1.pf4/stats_xf': [('most', 32, 16, 8, 2, 0), ('cheapest', 32, 14, 7, 2, 0)],
+    't2x1.res.c1.pf8/plain': [('most', 50, 8, 8, 1, 1)],
+    't2x1.res.c1.pf8/stats': [('most', 50, 8, 8, 1, 0), ('cheapest', 50, 5, 5, 1, 0)],
+    't2x1.res.c1.pf8/stats_xf': [('most', 50, 8, 8, 2, 0), ('cheapest', 50, 5, 5, 2, 0)],
+    't2x1.res.c4.pf4/plain': [('most', 32, 56, 8, 5, 1)],
+    't2x1.res.c4.pf8/plain': [('most', 84, 8, 8, 5, 1)],
+    't2x1.ring.c1.pf4/stats': [('most', 50, 16, 8, 5, 0), ('cheapest', 50, 10, 5, 5, 0)],
+    't2x1.ring.c1.pf8/plain': [('most', 50, 40, 8, 10, 1)],
+    't2x1.ring.c1.pf8/stats': [('most', 50, 24, 8, 10, 0), ('cheapest', 84, 4, 4, 8, 0)],
+    't2x1.ring.c1.pf8/stats_xf': [('most', 84, 7, 7, 6, 0), ('cheapest', 84, 4, 4, 6, 0)],
+    't2x1.ring.c4.pf8/plain': [('most', 32, 104, 8, 10, 1)],
+    't2x1.two.c1.pf8/stats': [('most', 84, 14, 7, 10, 0)],
+    't2x1.two.c1.pf8/stats_xf': [('most', 50, 104, 8, 16, 0), ('cheapest', 50, 100, 4, 16, 0)],
+    't2x1.two.c4.pf8/plain': [('most', 32, 344, 8, 15, 1)],
+    't2x2.two.c1.pf8/plain': [('most', 84, 80, 8, 7, 1)],
+    't3x1.res.c1.pf8/plain': [('most', 32, 56, 8, 6, 1)],
+    't3x1.res.c1.pf8/stats': [('most', 32, 56, 8, 8, 0), ('cheapest', 50, 20, 4, 8, 0)],
+    't3x1.res.c1.pf8/stats_xf': [('most', 32, 56, 8, 6, 0), ('cheapest', 32, 50, 5, 6, 0)],
+    't3x1.ring.c1.pf4/stats': [('most', 84, 8, 8, 5, 0), ('cheapest', 50, 20, 4, 5, 0)],
+    't3x1.ring.c1.pf4/stats_xf': [('most', 50, 24, 8, 6, 0), ('cheapest', 50, 20, 4, 6, 0)],
+    't3x1.ring.c1.pf8/plain': [('most', 84, 8, 8, 6, 1)],
+    't3x1.ring.c1.pf8/stats': [('most', 84, 8, 8, 8, 0), ('cheapest', 84, 8, 4, 8, 0)],
+    't3x1.ring.c1.pf8/stats_xf': [('most', 84, 8, 8, 6, 0), ('cheapest', 84, 8, 4, 6, 0)],
+    't3x1.ring.c4.pf8/plain': [('most', 32, 200, 8, 10, 1)],
+    't3x2.two.c1.pf4/stats': [('most', 50, 208, 8, 5, 0), ('cheapest', 50, 205, 5, 5, 0)],
+    't3x2.two.c1.pf4/stats_xf': [('most', 32, 512, 8, 6, 0), ('cheapest', 32, 512, 4, 6, 0)],
+    't3x2.two.c1.pf8/plain': [('most', 50, 208, 8, 6, 1)],
+    't3x2.two.c1.pf8/stats': [('most', 50, 208, 8, 8, 0), ('cheapest', 50, 205, 5, 8, 0)],
+    't3x2.two.c1.pf8/stats_xf': [('most', 50, 208, 8, 6, 0), ('cheapest', 50, 205, 5, 6, 0)],
+    't4x1.ring.c1.pf8/stats': [('most', 50, 72, 8, 17, 0), ('cheapest', 50, 68, 4, 17, 0)],
+    't4x1.two.c1.pf8/stats': [('most', 32, 328, 8, 17, 0)],
+    't5x1.res.c1.pf8/plain': [('most', 50, 200, 8, 15, 1)],
+    't5x1.ring.c1.pf4/stats': [('most', 128, 16, 8, 10, 0), ('cheapest', 128, 14, 7, 10, 0)],
+    't5x1.ring.c1.pf4/stats_xf': [('most', 32, 200, 8, 11, 0)],
+    't5x1.ring.c1.pf8/plain': [('most', 50, 72, 8, 11, 1)],
+    't5x1.ring.c1.pf8/stats': [('most', 50, 72, 8, 13, 0), ('cheapest', 50, 68, 4, 13, 0)],
+    't5x1.ring.c1.pf8/stats_xf': [('most', 50, 72, 8, 11, 0), ('cheapest', 50, 68, 4, 11, 0)],
+    't5x1.ring.c4.pf8/plain': [('most', 128, 56, 8, 15, 1)],
+    't5x1.two.c1.pf4/stats': [('most', 128, 24, 8, 10, 0), ('cheapest', 128, 18, 3, 10, 0)],
+    't5x1.two.c1.pf8/plain': [('most', 50, 88, 8, 11, 1)],
+    't5x1.two.c1.pf8/stats': [('most', 50, 88, 8, 13, 0), ('cheapest', 50, 87, 3, 13, 0)],
+    't5x1.two.c1.pf8/stats_xf': [('most', 50, 88, 8, 11, 0), ('cheapest', 50, 87, 3, 11, 0)],
+    't5x1.two.c4.pf8/plain': [('most', 128, 72, 8, 15, 1)],
+    't5x2.two.c1.pf8/plain': [('most', 128, 128, 8, 11, 1)],
+    't5x2.two.c1.pf8/stats': [('most', 128, 128, 8, 13, 0), ('cheapest', 128, 128, 4, 13, 0)],
+    't5x2.two.c1.pf8/stats_xf': [('most', 128, 128, 8, 11, 0), ('cheapest', 128, 128, 4, 11, 0)],
+    'wg1x2.pf4.m0/plain': [('most', 32, 8, 8, 0, 2)],
+    'wg1x2.pf4/plain': [('most', 32, 48, 8, 0, 2)],
+    'wg1x2.pf4/xf': [('most', 128, 8, 8, 2, 2), ('cheapest', 128, 3, 3, 2, 2)],
+    'wg1x2.pf8.m1/plain': [('most', 32, 8, 8, 1, 2)],
+    'wg1x2.pf8.m1/xf': [('most', 32, 8, 8, 2, 2), ('cheapest', 32, 3, 3, 2, 2)],
+    'wg1x2.pf8/plain': [('most', 50, 28, 7, 1, 2)],
+    'wg1x2.pf8/xf': [('most', 50, 28, 7, 2, 2), ('cheapest', 32, 65, 5, 2, 2)],
+    'wg1x3.pf4.m2/plain': [('most', 84, 6, 6, 5, 2)],
+    'wg1x3.pf4/plain': [('most', 84, 8, 8, 5, 2)],
+    'wg1x3.pf8.m3/plain': [('most', 32, 8, 8, 8, 2)],
+    'wg1x3.pf8.m3/xf': [('most', 32, 8, 8, 6, 2), ('cheapest', 32, 3, 3, 6, 2)],
+    'wg1x3.pf8/plain': [('most', 50, 24, 8, 13, 2)],
+    'wg1x3.pf8/xf': [('most', 50, 24, 8, 11, 2), ('cheapest', 128, 3, 3, 16, 2)],
+    'wg1x5.pf4/plain': [('most', 32, 48, 8, 13, 2)],
+    'wg1x5.pf4/xf': [('most', 32, 48, 8, 11, 2), ('cheapest', 32, 48, 3, 11, 2)],
+    'wg1x5.pf8/plain': [('most', 32, 48, 8, 18, 2)],
+    'wg1x5.pf8/xf': [('most', 32, 56, 8, 16, 2), ('cheapest', 32, 48, 3, 16, 2)],
+    'wg2x2.pf8/plain': [('most', 32, 72, 8, 1, 2)],
+    'wg2x2.pf8/xf': [('most', 32, 72, 8, 2, 2), ('cheapest', 84, 10, 5, 2, 2)],
+    'wg2x3.pf8/plain': [('most', 32, 48, 8, 8, 2)],
+    'wg2x3.pf8/xf': [('most', 32, 48, 8, 6, 2), ('cheapest', 128, 3, 3, 6, 2)],
+    'wg2x5.pf8/xf': [('most', 32, 48, 8, 16, 2)],
+    'wg3x2.pf8/plain': [('most', 32, 48, 8, 1, 2)],
+    'wg3x2.pf8/xf': [('most', 32, 48, 8, 2, 2), ('cheapest', 32, 48, 3, 2, 2)],
+    'wgq3.pf8/plain': [('most', 32, 192, 8, 1, 2)],
+    'wgq3.pf8/xf': [('most', 32, 192, 8, 2, 2), ('cheapest', 50, 77, 7, 2, 2)],
+    'wx1x1/plain': [('most', 32, 104, 8, 11, 1)],
+    'wx1x1/stats': [('most', 32, 104, 8, 13, 0), ('cheapest', 32, 104, 4, 13, 0)],
+    'wx3x1/plain': [('most', 32, 128, 8, 6, 1)],
+    'wx3x1/stats': [('most', 32, 128, 8, 8, 0), ('cheapest', 32, 128, 4, 8, 0)],
+}
+
+
+GROUP_LIST = [(k, c[0], tuple(c[1:])) for k in sorted(GROUP_CASES) for c in GROUP_CASES[k]]
+GROUP_CONV = [c for c in GROUP_LIST if not c[0].startswith("wg") and not c[0].endswith("/stats_xf")]
+GROUP_XF = [c for c in GROUP_LIST if c[0].endswith("/stats_xf")]
+GROUP_WGRAD = [c for c in GROUP_LIST if c[0].startswith("wg")]
+
+
 # how tests/test_gpu_layers.py runs the cases (tests/test_cpu_forms.py checks that together they are every key of COVERED and that the GPU
 # file parametrizes its tests with exactly these lists): integer-exact conv cases, the input-transform cases (tier 2 against float64
 # BatchNorm), the integer-exact weight-gradient cases
@@ -603,8 +774,17 @@ def format_tables(lib):
     COVERED.update(cov)
     out = ["COVERED = {"]
     out += ["    %r: %r," % (k, tuple(cov[k])) for k in sorted(cov)]
-    out += ["}", "", "EDGE_CASES = {"]
-    ec = edge_cases(lib)
+    out += ["}", ""]
+    return "\n".join(out + _format_case_table("EDGE_CASES", edge_cases(lib)))
+
+
+def format_group_cases(lib):
+    """The text of GROUP_CASES for the present planner."""
+    return "\n".join(_format_case_table("GROUP_CASES", group_cases(lib)))
+
+
+def _format_case_table(name, ec):
+    out = ["%s = {" % name]
     for k in sorted(ec):
         line = "    %r: [" % k
         for i, c in enumerate(ec[k]):
@@ -615,7 +795,7 @@ def format_tables(lib):
             line += item if line.endswith("[") else " " + item
         out.append(line)
     out.append("}")
-    return "\n".join(out)
+    return out
 
 
 if __name__ == "__main__":
@@ -624,4 +804,4 @@ if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import ocl_amd  # noqa: F401
     from ocl_amd import ffi
-    print(format_tables(ffi.lib()))
+    print(format_group_cases(ffi.lib()) if sys.argv[1:] == ["groups"] else format_tables(ffi.lib()))

@@ -61,7 +61,9 @@ def test_the_table_holds_the_passes_it_is_meant_to():
     # the C ABI matrix
     assert WC.NETCHECK_MODES == [{}, {"OCL_WGRAD_Q": "0"}, {"OCL_WGRAD_MULTI": "0"}, {"OCL_DY_KEEP": "0"}, {"OCL_BN_CHAN": "0"},
                                  {"OCL_SINGLE_STREAM": "1"}, {"OCL_GRAPH": "1"}]
-    assert WC.NETCHECK_CASES == [(20, 2, 32, 0), (6, 2, 84, 1)] and WC.NETCHECK_DEFAULT_ONLY == [(220, 2, 32, 1)]
+    assert WC.NETCHECK_CASES == [(20, 2, 32, 0), (6, 2, 84, 1), (9, 3, 32, 1)] and WC.NETCHECK_DEFAULT_ONLY == [(220, 2, 32, 1)]
+    # passes of more than two BatchNorm groups: the backward's reduce + apply arena (tests/test_gpu_ws_poison.py, off_bsums)
+    assert {(c["model"], c["n"], c["groups"]) for c in by_kind["taped"]} >= {("scr_c100", 9, 3), ("er_c100", 12, 4)}
 
 
 def test_the_gpu_files_run_the_whole_table():

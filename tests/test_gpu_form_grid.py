@@ -12,8 +12,13 @@ tests/test_gpu_layers.py:
 The nine forms the dense grid added to layer_forms.COVERED run in the per-form tests of tests/test_gpu_layers.py; the whole passes at 67,
 70 and 342 images are cases of tests/test_gpu_net.py::test_train_forward_backward_vs_oracle.
 
+The same three bodies run the cases of layer_forms.GROUP_CASES: every form a pass of three to eight BatchNorm groups plans, at the cheapest
+pass with the most groups and, where the epilogue or the staging reads the group, at the cheapest pass of all.  The bodies take the group
+count from the layer's description and compare every group's accumulator cells.
+
 With OCL_PARITY_REPORT=<file> the tier-2 margins and every case's wall time go to form_grid_parity.txt next to it
-(profiles/form_grid_parity.txt)."""
+(profiles/form_grid_parity.txt), those of the many-group cases to many_groups_form_parity.txt (a section of
+profiles/many_groups_parity.txt)."""
 import os
 import time
 
@@ -26,6 +31,7 @@ import test_gpu_layers as TL
 pytestmark = pytest.mark.gpu
 
 REPORT = []
+GROUP_REPORT = []
 
 
 def _id(c):
@@ -50,6 +56,14 @@ def lib(cuda):
             f.write("# %d cases, %.1f s in all (slowest %.2f s)\n" % (len(REPORT), total, max(r[2] for r in REPORT)))
             f.write("%-72s %-8s %8s %8s\n" % ("case", "tier", "seconds", "ratio"))
             for case, tier, sec, ratio in REPORT:
+                f.write("%-72s %-8s %8.2f %8s\n" % (case, tier, sec, "" if ratio is None else "%.3f" % ratio))
+    if path and GROUP_REPORT:
+        with open(os.path.join(os.path.dirname(os.path.abspath(path)), "many_groups_form_parity.txt"), "w") as f:
+            f.write("# every form a pass of 3 .. 8 BatchNorm groups plans (layer_forms.GROUP_CASES): tier 1 cases are bit-equal or fail; tier 2\n"
+                    "# (/stats_xf) cases give their worst error / bound (must be < 1); seconds are wall time, float64 reference included\n")
+            f.write("# %d cases, slowest %.2f s\n" % (len(GROUP_REPORT), max(r[2] for r in GROUP_REPORT)))
+            f.write("%-72s %-8s %8s %8s\n" % ("case", "tier", "seconds", "ratio"))
+            for case, tier, sec, ratio in GROUP_REPORT:
                 f.write("%-72s %-8s %8.2f %8s\n" % (case, tier, sec, "" if ratio is None else "%.3f" % ratio))
 
 
@@ -88,6 +102,35 @@ def test_edge_wgrad_form_is_exact(lib, at, case):
     if ".m" in key:
         TL._wgrad_form_is_exact(lib, key, True)
     REPORT.append((_id(case), "1", time.perf_counter() - t0, None))
+
+
+@pytest.mark.parametrize("case", LF.GROUP_CONV, ids=_id)
+def test_group_conv_form_is_exact(lib, at, case):
+    key, kind, where = case
+    at(where)
+    t0 = time.perf_counter()
+    TL._conv_form_is_exact(lib, key, 0)
+    GROUP_REPORT.append((_id(case), "1", time.perf_counter() - t0, None))
+
+
+@pytest.mark.parametrize("case", LF.GROUP_XF, ids=_id)
+def test_group_input_transform_against_float64_batchnorm(lib, at, case):
+    key, kind, where = case
+    at(where)
+    t0 = time.perf_counter()
+    ratio = TL._input_transform_against_float64_batchnorm(lib, key, 0)
+    GROUP_REPORT.append((_id(case), "2", time.perf_counter() - t0, ratio))
+
+
+@pytest.mark.parametrize("case", LF.GROUP_WGRAD, ids=_id)
+def test_group_wgrad_form_is_exact(lib, at, case):
+    key, kind, where = case
+    at(where)
+    t0 = time.perf_counter()
+    TL._wgrad_form_is_exact(lib, key, False)
+    if ".m" in key:
+        TL._wgrad_form_is_exact(lib, key, True)
+    GROUP_REPORT.append((_id(case), "1", time.perf_counter() - t0, None))
 
 
 @pytest.mark.parametrize("kind", ["last_image", "last_pixel"])

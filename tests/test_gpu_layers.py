@@ -601,6 +601,12 @@ def _input_transform_against_float64_batchnorm(lib, key, det):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # BatchNorm
 # ---------------------------------------------------------------------------------------------------------------------------------
+def _err_ratio(got, ref, rtol, atol):
+    """Worst |got - ref| / (atol + rtol * |ref|): what assert_allclose holds below 1 (printed for the parity records)."""
+    got, ref = got.double().cpu().numpy(), ref.numpy()
+    return float((np.abs(got - ref) / (atol + rtol * np.abs(ref))).max())
+
+
 def _bn_case(g, n, hw, c, groups):
     y = (torch.randn((n, hw, hw, c), generator=g, dtype=torch.float64) * 1.5 + 0.2).float().double()
     gamma = (1 + 0.2 * torch.randn(c, generator=g, dtype=torch.float64)).float().double()
@@ -610,7 +616,9 @@ def _bn_case(g, n, hw, c, groups):
 
 @pytest.mark.parametrize("det", [0, 1])
 @pytest.mark.parametrize("n,hw,c,groups,two,frozen", [(10, 32, 20, 2, False, False), (7, 16, 40, 1, True, False), (22, 8, 80, 2, True, False),
-                                                     (5, 4, 160, 1, False, True), (3, 11, 160, 1, True, True)])
+                                                     (5, 4, 160, 1, False, True), (3, 11, 160, 1, True, True),
+                                                     # three and eight groups: one running-statistics update per group, in group order
+                                                     (6, 4, 160, 3, True, False), (8, 8, 20, 8, False, False), (8, 4, 20, 8, True, False)])
 def test_bn_forward_against_float64(lib, det, n, hw, c, groups, two, frozen):
     from ocl_amd import ffi
     lib.ocl_set_deterministic(det)
@@ -618,6 +626,11 @@ def test_bn_forward_against_float64(lib, det, n, hw, c, groups, two, frozen):
         g = torch.Generator().manual_seed(n + c)
         y, gamma, beta = _bn_case(g, n, hw, c, groups)
         yb, gb, bb = _bn_case(g, n, hw, c, groups)
+        if groups > 2:
+            # group means of alternating sign and growing size (-1, 2, -3, ...): the running recurrence weighs group i by 0.1 * 0.9^(G - 1 - i),
+            # so an update in another order, or one that stops early, is off by far more than the bound
+            off = torch.tensor([(-1.0) ** (i + 1) * (i + 1) for i in range(groups)], dtype=torch.float64).repeat_interleave(n // groups)
+            y, yb = (y + off[:, None, None, None]).float().double(), (yb - 0.5 * off[:, None, None, None]).float().double()
         a = ffi.TestBnFwdArgs(m_per_group=n // groups * hw * hw, groups=groups, c=c, relu=1, momentum=0.1, eps=1e-5)
         keep = {}
 
@@ -669,6 +682,9 @@ def test_bn_forward_against_float64(lib, det, n, hw, c, groups, two, frozen):
             erm, erv = torch.zeros(c, dtype=torch.float64), torch.ones(c, dtype=torch.float64)
             for gi in range(groups):
                 erm, erv = 0.9 * erm + 0.1 * mean[gi], 0.9 * erv + 0.1 * uvar[gi]
+            print("BN fwd err / bound: z %.3f save_mean %.3f save_invstd %.3f running_mean %.3f running_var %.3f" % (
+                _err_ratio(z, want, 2e-5, 2e-5), _err_ratio(keep["save_mean"], mean, 1e-6, 1e-6), _err_ratio(keep["save_invstd"], invstd, 1e-5, 0.0),
+                _err_ratio(keep["running_mean"], erm, 1e-5, 1e-6), _err_ratio(keep["running_var"], erv, 1e-5, 1e-6)))
             np.testing.assert_allclose(keep["running_mean"].double().cpu().numpy(), erm.numpy(), rtol=1e-5, atol=1e-6)
             np.testing.assert_allclose(keep["running_var"].double().cpu().numpy(), erv.numpy(), rtol=1e-5, atol=1e-6)
             assert int(keep["nbt"][0]) == groups
@@ -700,7 +716,12 @@ def _bn_bwd_ref(dz, zmask, y, groups, gamma, frozen_invstd=None):
     (6, 16, 40, 2, 1, 1, 2061), (10, 32, 20, 2, 2, 1, 2062),           # bn_bwd_fused_kernel<6, 1|2>
     (12, 16, 80, 1, 2, 1, 2062),
     (40, 32, 20, 2, 1, 1, 2121),                                       # bn_bwd_fused_kernel<12, 1>
-    (10, 32, 20, 2, 1, 0, 3001), (10, 16, 40, 2, 2, 0, 3002)])         # reduce + apply
+    (10, 32, 20, 2, 1, 0, 3001), (10, 16, 40, 2, 2, 0, 3002),          # reduce + apply
+    # three to eight groups: reduce + apply whatever one_pass says (the one-pass and per-channel kernels hold two groups), the sums of two
+    # sets addressed [set][G][2][C]; the smallest maps, one or two images per group
+    (3, 4, 160, 3, 1, 1, 3001), (8, 8, 20, 4, 1, 1, 3001), (8, 4, 160, 8, 1, 0, 3001), (16, 4, 20, 8, 1, 1, 3001),
+    (6, 8, 20, 3, 2, 1, 3002), (4, 4, 160, 4, 2, 1, 3002), (8, 8, 160, 4, 2, 0, 3002),
+    (10, 8, 160, 5, 2, 1, 3002), (5, 4, 20, 5, 2, 0, 3002), (8, 4, 20, 8, 2, 1, 3002)])
 def test_bn_backward_paths_against_float64(lib, det, n, hw, c, groups, nsets, one_pass, want):
     from ocl_amd import ffi
     lib.ocl_set_deterministic(det)
@@ -725,6 +746,9 @@ def test_bn_backward_paths_against_float64(lib, det, n, hw, c, groups, nsets, on
         print("BN path", path, "n=%d hw=%d c=%d groups=%d nsets=%d" % (n, hw, c, groups, nsets))
         assert path == want, (path, want)
         for (dy, dgm, dbt), ts in refs:
+            print("BN bwd err / bound: dy %.3f dgamma %.3f dbeta %.3f" % (
+                _err_ratio(ts[5], dy, 1e-4, 2e-5 * float(dy.abs().max())), _err_ratio(ts[6], dgm, 1e-4, 1e-4 * float(dgm.abs().max())),
+                _err_ratio(ts[7], dbt, 1e-4, 1e-4 * float(dbt.abs().max()))))
             np.testing.assert_allclose(ts[5].double().cpu().numpy(), dy.numpy(), rtol=1e-4, atol=2e-5 * float(dy.abs().max()))
             np.testing.assert_allclose(ts[6].double().cpu().numpy(), dgm.numpy(), rtol=1e-4, atol=1e-4 * float(dgm.abs().max()))
             np.testing.assert_allclose(ts[7].double().cpu().numpy(), dbt.numpy(), rtol=1e-4, atol=1e-4 * float(dbt.abs().max()))
@@ -773,6 +797,36 @@ def test_bn_backward_frozen_and_mask_from_y(lib):
     inv32 = invstd.float().double()
     want = dz * (zm > 0) * gamma * inv32[0]
     np.testing.assert_allclose(ts2[7].double().cpu().numpy(), want.numpy(), rtol=1e-5, atol=1e-6)
+    # three and eight groups (every bn1 backward of such a pass): reduce + apply with mask_from_y, and accumulating onto a preset gradient
+    for n, hw, c, groups, accumulate in [(6, 8, 20, 3, 0), (3, 4, 160, 3, 1), (8, 4, 160, 8, 1)]:
+        dz = torch.randn((n, hw, hw, c), generator=g, dtype=torch.float64).float().double()
+        y, gamma, beta = _bn_case(g, n, hw, c, groups)
+        _, mean, invstd, _ = _bn_ref(y, groups, gamma, beta)
+        dg0 = torch.randn(c, generator=g, dtype=torch.float64).float().double() * accumulate
+        db0 = torch.randn(c, generator=g, dtype=torch.float64).float().double() * accumulate
+        a = ffi.TestBnBwdArgs(m_per_group=n // groups * hw * hw, groups=groups, c=c, nsets=1, mask_from_y=1, one_pass=1, accumulate=accumulate)
+        ts = [dev(t.float()) for t in (dz, y, mean, invstd, gamma, beta)] + [dev(torch.full(y.shape, float("nan"))), dev(dg0.float()), dev(db0.float())]
+        a.dz = p(ts[0])
+        for f, t in zip(("y", "mean", "invstd", "gamma", "beta", "dy", "dgamma", "dbeta"), ts[1:]):
+            getattr(a, f)[0] = t.data_ptr()
+        path = lib.ocl_test_bn_bwd(C.byref(a), None)
+        assert path == 3001, (path, lib.ocl_last_error())
+        mb, ib = mean.repeat_interleave(n // groups, 0)[:, None, None, :], invstd.repeat_interleave(n // groups, 0)[:, None, None, :]
+        zpre = (y - mb) * ib * gamma + beta
+        dy, dgm, dbt = _bn_bwd_ref(dz, zpre, y, groups, gamma)
+        amb = zpre.abs() < 1e-5
+        # a group without a near-zero pre-activation compares element-wise (a mask decision moves the whole group's means)
+        ok = ~amb.reshape(groups, -1).any(dim=1).repeat_interleave(n // groups, 0)
+        assert bool(ok.any())
+        np.testing.assert_allclose(ts[6].double().cpu()[ok].numpy(), dy[ok].numpy(), rtol=1e-4, atol=2e-5 * float(dy.abs().max()))
+        xhat = (y - mb) * ib
+        slack_g = (dz.abs() * xhat.abs() * amb).sum(dim=(0, 1, 2)).numpy()
+        slack_b = (dz.abs() * amb).sum(dim=(0, 1, 2)).numpy()
+        got_g, got_b = ts[7].double().cpu().numpy() - dg0.numpy(), ts[8].double().cpu().numpy() - db0.numpy()
+        lim_g = slack_g + 1e-4 * np.abs(dgm.numpy()) + 1e-4 * float(dgm.abs().max()) + 2 * U * accumulate * (np.abs(dg0.numpy()) + np.abs(dgm.numpy()))
+        lim_b = slack_b + 1e-4 * np.abs(dbt.numpy()) + 1e-4 * float(dbt.abs().max()) + 2 * U * accumulate * (np.abs(db0.numpy()) + np.abs(dbt.numpy()))
+        assert np.all(np.abs(got_g - dgm.numpy()) <= lim_g), ("dgamma", n, hw, c, groups)
+        assert np.all(np.abs(got_b - dbt.numpy()) <= lim_b), ("dbeta", n, hw, c, groups)
 
 
 @pytest.mark.parametrize("det", [0, 1])

@@ -70,6 +70,15 @@ CASES = [
     ("ER", "cifar100", None, 67, 1),        # layer 1's weight gradient on wg1x2.pf8 (65 .. 71 images): ER, batch 10 + 57 memory images
     ("SCR", "cifar100", "mlp", 70, 2),      # the same with the input transform: SCR with eps_mem_batch 25
     ("ER", "cifar100", None, 342, 1),       # layer 4's shortcut on t4x1.two.c1.pf8/stats, its merged data gradient on t2x1.two.c4.pf8
+    # passes of three to eight BatchNorm groups (model.forward_views of as many views): every BatchNorm backward on the reduce + apply pair,
+    # the per-group tables of the input transform and of the weight gradient above index 1, several group changes inside a workgroup's tiles
+    ("SCR", "cifar100", "mlp", 9, 3),       # three images per group
+    ("SCR", "cifar100", "mlp", 12, 4),      # two BatchNorms sharing dL/dz fill a reduction arena of kGmax * 2 * C cells exactly
+    ("SCR", "cifar100", "mlp", 15, 5),      # ... and need the second half of the arena (2 * kGmax * 2 * C cells)
+    ("SCR", "cifar100", "mlp", 8, 8),       # one image per group: 16 pixels per group at layer 4
+    ("ER", "mini_imagenet", None, 6, 3),    # 84 x 84
+    ("ER", "cifar100", None, 48, 8),        # layers 16 and 19: the weight gradient on wg2x5.pf8/xf (no pass of one or two groups plans it)
+    ("SCR", "cifar100", "mlp", 200, 8),     # layers 11 and 14 on t5x1.ring.c1.pf4/stats_xf (the same): the cheapest pass that plans it
 ]
 
 BLOCKS = ["layer%d.%d" % (l, b) for l in range(1, 5) for b in range(2)]
@@ -134,11 +143,13 @@ def train_forward_backward_vs_oracle(cuda, agent, data, head, n, groups, images=
         probe.forward(xt[:per])
     shapes = {k: (n,) + tuple(v.shape[1:]) for k, v in probe.pre_act.items()}
     masks = engine_masks(m, shapes, pre)
-    outs, n_mis, n_tot, worst_amb = [], 0, 0, 0.0
+    outs, recs, n_mis, n_tot, worst_amb = [], [], 0, 0, 0.0
     for g in range(groups):
         net.mask_override = {k: v[g * per:(g + 1) * per] for k, v in masks.items()}
         net.pre_act = {}
+        net.rec = {}
         outs.append(net.forward(xt[g * per:(g + 1) * per]))
+        recs.append(net.rec)
         for k, pa in net.pre_act.items():
             mis = (pa > 0).float() != net.mask_override[k]
             n_mis += int(mis.sum())
@@ -148,10 +159,10 @@ def train_forward_backward_vs_oracle(cuda, agent, data, head, n, groups, images=
     o_ref = torch.cat(outs, 0)
     print("relu pattern mismatches: %d of %d, worst |pre-activation| / max = %.2e" % (n_mis, n_tot, worst_amb))
     assert n_mis <= 5 + 2e-5 * n_tot and worst_amb < 1e-5, "activation patterns differ beyond fp32 round-off"
-    if groups == 1:
-        rows = layer_report(m, net.rec, n)
-        print("\n".join("%-40s %.3e" % r for r in rows))
-        assert max(r[1] for r in rows) < 1e-4, "raw conv outputs diverge: %s" % (max(rows, key=lambda r: r[1]),)
+    # (the oracle records one group per call: the engine's tape holds the groups one behind the other)
+    rows = layer_report(m, {name: torch.cat([r[name] for r in recs], 0) for name in recs[0]}, n)
+    print("\n".join("%-40s %.3e" % r for r in rows))
+    assert max(r[1] for r in rows) < 1e-4, "raw conv outputs diverge: %s" % (max(rows, key=lambda r: r[1]),)
     err_out = np.abs(out.detach().cpu().numpy() - o_ref.detach().numpy()).max()
     print("out err", err_out)
     assert err_out < 1e-4
@@ -185,6 +196,78 @@ def train_forward_backward_vs_oracle(cuda, agent, data, head, n, groups, images=
             assert relmax(sd_new[k].cpu().numpy(), st[k].numpy()) < 1e-4, k
         if k.endswith("num_batches_tracked"):
             assert int(sd_new[k]) == int(st[k]) == groups
+
+
+@pytest.mark.parametrize("groups", [1, 2, 3, 4, 5, 6, 7, 8])
+def test_a_taped_pass_of_any_group_count_trains_or_is_refused_before_any_launch(cuda, groups):
+    """ocl_net_forward accepts 1 .. 8 BatchNorm groups and tapes the pass: its backward must then either run to the end or be refused before
+    it has launched anything.  The gradient holds a sentinel in front of the backward (accumulating: every tensor is read-modify-written);
+    after a refusal every word of it is still the sentinel, after a success it is finite and sentinel + the gradient of a fresh engine's
+    overwriting backward, to fp32 rounding of the sum."""
+    rng = np.random.default_rng(40 + groups)
+    x = torch.from_numpy(rng.random((2 * groups, 3, 32, 32)).astype(np.float32)).to(cuda)
+    views = [x[2 * g:2 * g + 2] for g in range(groups)]
+    from ocl_amd import ops
+    ops.set_deterministic(True)      # (the two engines then compute the same pass bit for bit: no ReLU decision can differ between them)
+    try:
+        grads = _taped_backward_over_a_sentinel(cuda, groups, views)
+    finally:
+        ops.set_deterministic(False)
+    assert (grads[0] is None) == (grads[1] is None), "the same backward was refused once and ran once"
+    if grads[0] is not None:
+        g, acc = grads
+        assert np.isfinite(g).all() and np.isfinite(acc).all() and np.abs(g).max() > 0
+        # sentinel + g in fp32: the rounding of the sum (2^-24 relative; twice that for a kernel that adds the sentinel to a partial sum first),
+        # and the gradient bound of test_train_forward_backward_vs_oracle, 2e-4 of the largest entry, for the order of the terms
+        assert np.all(np.abs(acc - 3.0 - g) <= 2.0 ** -23 * (3.0 + np.abs(g)) + 2e-4 * np.abs(g).max())
+
+
+def _taped_backward_over_a_sentinel(cuda, groups, views):
+    grads = []
+    for sentinel in (None, 3.0):
+        m, _ = build("SCR", "cifar100", "mlp", cuda=cuda)
+        m.train()
+        out, tape = m.forward_views_taped(views)
+        dout = (torch.linspace(-1, 1, out.numel(), device=cuda).view_as(out) / out.shape[0]).contiguous()
+        m._attach_grads()
+        if sentinel is not None:
+            m.flat_grads().fill_(sentinel)
+            m._grads_fresh = False
+        torch.cuda.synchronize()
+        try:
+            m.backward_taped(tape, dout)
+        except RuntimeError:
+            torch.cuda.synchronize()
+            if sentinel is not None:
+                assert bool((m.flat_grads() == sentinel).all()), "a refused backward of %d groups wrote into the gradient" % groups
+            grads.append(None)
+            continue
+        torch.cuda.synchronize()
+        grads.append(m.flat_grads().double().cpu().numpy().copy())
+    return grads
+
+
+def test_three_group_passes_are_bit_reproducible(cuda):
+    """Deterministic mode: two fresh engines, the same 9 images in three BatchNorm groups -- output, flat gradient, running statistics and
+    num_batches_tracked are equal bit for bit (every BatchNorm backward of such a pass reduces through bn_bwd_reduce_kernel's cells)."""
+    from ocl_amd import ops
+    rng = np.random.default_rng(93)
+    x = torch.from_numpy(rng.random((9, 3, 32, 32)).astype(np.float32)).to(cuda)
+    ops.set_deterministic(True)
+    try:
+        runs = []
+        for _ in range(2):
+            m, _ = build("SCR", "cifar100", "mlp", cuda=cuda)
+            m.train()
+            out = m.forward_views([x[0:3], x[3:6], x[6:9]])
+            (out * torch.linspace(-1, 1, out.numel(), device=cuda).view_as(out)).sum().backward()
+            torch.cuda.synchronize()
+            runs.append([t.detach().cpu().numpy().copy() for t in (out, m.flat_grads(), m._running, m._nbt)])
+    finally:
+        ops.set_deterministic(False)
+    for a, b in zip(*runs):
+        assert a.tobytes() == b.tobytes()
+    assert np.abs(runs[0][1]).max() > 0 and int(runs[0][3].max()) == 3
 
 
 def test_gradient_accumulation_and_zero_grad_semantics(cuda):

@@ -41,6 +41,11 @@ first pass destroys nothing.
                                        backward leaves bsums_clean = false, so the next one clears.  No path reads a counter that was
                                        not cleared since the bind.  (The spin on the counter is bounded at 2^22 polls, and a counter
                                        of 0xFFFFFFFF ends the wait at once: wrong sums, not a hang, would be the symptom.)
+  off_bsums    backward reduce +       bn_bwd_reduce_kernel ACCUMULATES (fx_add) into [set][G][2][C] cells at barena_off, the front part of
+  (barena_off) apply sums, two sets    the arena (2 * kGmax * 2 * C cells per BatchNorm), bn_bwd_apply_kernel reads them: inside
+               of up to 8 groups       bsums_doubles and so inside the clears of the row above.  In the default mode only frozen tapes and
+                                       passes of three or more groups take this pair (the other kernels hold two groups): the
+                                       -views-taped-g3 / -g4 cases, netcheck's (9, 3, 32, 1) in every run-time mode
   off_pack     weight packs            upload_descs zeroes the whole arena once (hipMemsetAsync); pack_weights_kernel rewrites the
                                        layouts of pack_mask in every forward that packs and in a backward whose packs were displaced
                                        (repack); padding rows / columns of a pack are never written again and stay zero

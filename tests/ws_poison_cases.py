@@ -61,6 +61,10 @@ def _build():
     cases.append(_direct("er_c100-train-no-grad", "er_c100", "no_grad", claims=("I5",), n=PC.I5_N))
     cases.append(_direct("scr_c100-views-taped", "scr_c100", "taped", n=14, groups=2))
     cases.append(_direct("er_c100-views-taped", "er_c100", "taped", n=20, groups=2))
+    # three and four BatchNorm groups: every BatchNorm backward is the reduce + apply pair, whose sums lie in the front part of off_bsums
+    # (barena_off) -- cells no default-mode pass of one or two groups accumulates into
+    cases.append(_direct("scr_c100-views-taped-g3", "scr_c100", "taped", n=9, groups=3))
+    cases.append(_direct("er_c100-views-taped-g4", "er_c100", "taped", n=12, groups=4))
     cases.append(_direct("er_c100-same-weights", "er_c100", "same_weights", n=12))
     # a second, accumulating backward (two live tapes: the second backward clears the statistics arena itself), a preset gradient,
     # a refused backward -- and the row of all intruders, once
@@ -101,5 +105,5 @@ def pass_order_kinds():
 # C ABI (csrc/netcheck, NETCHECK_WS_FILL): run-time modes and passes; the 220-view pass runs in the default mode only
 NETCHECK_MODES = [{}, {"OCL_WGRAD_Q": "0"}, {"OCL_WGRAD_MULTI": "0"}, {"OCL_DY_KEEP": "0"}, {"OCL_BN_CHAN": "0"}, {"OCL_SINGLE_STREAM": "1"},
                   {"OCL_GRAPH": "1"}]
-NETCHECK_CASES = [(20, 2, 32, 0), (6, 2, 84, 1)]
+NETCHECK_CASES = [(20, 2, 32, 0), (6, 2, 84, 1), (9, 3, 32, 1)]
 NETCHECK_DEFAULT_ONLY = [(220, 2, 32, 1)]

@@ -631,14 +631,11 @@ int bn_bwd_last_path() { return g_bn_bwd_last_path; }
 int launch_bn_bwd(const BnBwdArgs& a, hipStream_t s) {
     OCL_REQUIRE(a.nsets == 1 || a.nsets == 2, "bn_bwd: nsets=%d", a.nsets);
     const int C4 = a.C / 4, PT = 256 / C4;
-    if (g_bn_fused < 0) {
-        const char* e = getenv("OCL_BN_FUSED");
-        g_bn_fused = e ? atoi(e) : 1;
-    }
+    if (g_bn_fused < 0) g_bn_fused = env_int("OCL_BN_FUSED", 1);
     // small maps: one workgroup per channel quad, no cross-workgroup reduction (bn_bwd_chan_kernel; OCL_BN_CHAN=0: off).  Gate: ONE unit per
     // thread (all groups' pixels <= 512: layer 4 up to 32 images) and >= 16 channel quads; at two units per thread it is neutral (6 x 84x84) or
     // loses (64 images in two groups: +7.5 us per pass), at four (layer 3 of a 20-image pass) it loses -- profiles/r6_bn_chan_ab.txt
-    static const bool bn_chan = [] { const char* e = getenv("OCL_BN_CHAN"); return !(e && e[0] == '0'); }();
+    static const bool bn_chan = env_not_off("OCL_BN_CHAN");
     if (bn_chan && g_bn_fused && !a.frozen && g_bn_bwd_phase == 0 && a.G <= 2 && C4 >= 16 && a.m_per_group * a.G <= kBnChanThreads) {
         ProfScope ps(PROF_BN, s);
         g_bn_bwd_last_path = 1010 + a.nsets;

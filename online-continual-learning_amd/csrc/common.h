@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
 #include "../../include/ocl_hip.h"
 
 namespace ocl {
@@ -60,6 +61,19 @@ unsigned* async_error_word_device();        // device-visible address (nullptr i
 int check_async_error(const char* where);   // OCL_OK, or OCL_ERR_STATE with the message set and the word cleared
 // small host -> device upload through the pinned staging ring (runtime.hip): asynchronous on `s`, `host` reusable on return
 int upload_small(const void* host, size_t nbytes, void* dev, hipStream_t s);
+
+// ---- run-time switches ----------------------------------------------------------------------------
+// Every OCL_* / KBENCH_* switch is an environment variable read through one of these three; a site keeps its value in a
+// `static const`, so a process reads each switch once.           unset   "0"   "1"
+//   env_on       measurement modes, off by default:                off    off   on    (first character '1')
+//   env_not_off  product paths that can be switched off for A/B:   on     off   on    (first character not '0')
+//   env_int      numbers (atoi), and the planner's kernel-family switches, spelled `env_int(name, 1) != 0`: unlike env_not_off they
+//                read the whole number, so "00" and "" are off and "01" is on (OCL_CONV_S / _Q4 / _PIPE / _WX)
+static inline bool env_on(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
+static inline bool env_not_off(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
+static inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+// OCL_LOG_PLANS=1: one line on stderr per plan made (host time): what a first-seen shape costs a running loop
+inline bool log_plans() { static const bool v = env_on("OCL_LOG_PLANS"); return v; }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }

@@ -272,7 +272,7 @@ static int plan_conv_s(const ConvGeomDesc& g, ConvPlan* p) {
     // One pixel tile per workgroup; two (every weight quad feeds two MFMAs: half the weight and table bytes per MFMA, twice the patch per
     // wave) on the 8x8 lattices of layer 3 once the one-tile grid has >= 800 workgroups -- 100 images: 14.6 vs 17.4 us, 150: 21.8 vs
     // 24.1; on layer 4 (two whole images per workgroup) it only pays around 150 images (profiles/r3_conv_s_ab.md).
-    static const int env_nt = [] { const char* e = getenv("OCL_CONV_S_NT"); return e ? atoi(e) : 0; }();   // measurement knob: 1 / 2 = always
+    static const int env_nt = env_int("OCL_CONV_S_NT", 0);   // measurement knob: 1 / 2 = always
     ConvPlan q1 = *p;
     const int r1 = plan_conv_s_nt(g, &q1, 1);
     const bool want2 = env_nt ? env_nt == 2 : (r1 == OCL_OK && g.LH * g.LW > 16 && (int64_t)q1.grid_x * q1.grid_y >= 800);
@@ -294,7 +294,7 @@ static int plan_conv_t(const ConvGeomDesc& g, ConvPlan* p) {
     {   // wave-autonomous tiles over resident weights (convw.hip): no workgroup barrier between the prologue and the statistics flush
         // OCL_CONV_W: 0 = never, 1 (default) = where its specialised form exists and measured faster (profiles/r6_convw_vs_planner.txt: the 3x3
         // stride-1 convolutions of 40 and 80 channels from ~100 images on), 2 = wherever it fits (A/B reference of tests/test_gpu_ring.py)
-        static const int env_cw = [] { const char* e = getenv("OCL_CONV_W"); return e ? atoi(e) : 1; }();
+        static const int env_cw = env_int("OCL_CONV_W", 1);
         if (g.force_cw > 0 || (g.force_cw == 0 && env_cw > 0 && !g.force_MT && !g.force_NT && g.force_cs <= 0 && g.force_q4 <= 0)) {
             ConvPlan q = *p;
             if (plan_conv_w(g, &q) == OCL_OK) {
@@ -310,7 +310,7 @@ static int plan_conv_t(const ConvGeomDesc& g, ConvPlan* p) {
         }
     }
     {   // few output pixels behind a deep K (layers 3 - 4 of a replay-sized pass): K split over the waves
-        static const bool env_cs = [] { const char* e = getenv("OCL_CONV_S"); return !(e && atoi(e) == 0); }();
+        static const bool env_cs = env_int("OCL_CONV_S", 1) != 0;
         if (g.force_cs > 0 || (g.force_cs == 0 && env_cs && !g.force_MT && !g.force_NT)) {
             ConvPlan q = *p;
             if (plan_conv_s(g, &q) == OCL_OK) {
@@ -320,7 +320,7 @@ static int plan_conv_t(const ConvGeomDesc& g, ConvPlan* p) {
         }
     }
     {   // <= 20 output channels: the 4x4x1 form (no channel / K padding) where it fits and the launch is large enough
-        static const bool env_q4 = [] { const char* e = getenv("OCL_CONV_Q4"); return !(e && atoi(e) == 0); }();
+        static const bool env_q4 = env_int("OCL_CONV_Q4", 1) != 0;
         if (g.force_q4 > 0 || (g.force_q4 == 0 && env_q4 && !g.force_MT && !g.force_NT)) {
             ConvPlan q = *p;
             if (plan_conv_q(g, &q) == OCL_OK) {
@@ -351,7 +351,7 @@ static int plan_conv_t(const ConvGeomDesc& g, ConvPlan* p) {
     if (MT < 1 || MT > 5 || NT < 1 || NT > 2 || MT > nt16) return OCL_ERR_ARG;
     if (g.ncls > 1 && NT != 1) return OCL_ERR_ARG;   // (a forced NT = 2: conv_t_kernel has output classes with one pixel tile per wave only)
     // staged-weight schedule: the three-buffer ring unless OCL_CONV_PIPE=0 asks for the two-buffer one (plan constant: read once)
-    static const bool env_pipe = [] { const char* e = getenv("OCL_CONV_PIPE"); return !(e && atoi(e) == 0); }();
+    static const bool env_pipe = env_int("OCL_CONV_PIPE", 1) != 0;
     const bool pipe = g.force_pipe > 0 || (g.force_pipe == 0 && env_pipe);
     size_t lds = convt_layout(g, a, MT, NT, pipe);
     if (!lds && NT == 2 && !g.force_NT) { NT = 1; lds = convt_layout(g, a, MT, NT, pipe); }
@@ -549,8 +549,7 @@ int conv_plan_finalize(ConvPlan* p, PlanArena* arena, hipStream_t s) {
         void* c = nullptr;
         OCL_HIP(hipMalloc(&c, cap));
         {
-            static const bool log_plans = [] { const char* e = getenv("OCL_LOG_PLANS"); return e && e[0] == '1'; }();
-            if (log_plans) fprintf(stderr, "[ocl] plan-table arena: chunk %zu allocated (%zu bytes)\n", arena->chunks.size() + 1, cap);
+            if (log_plans()) fprintf(stderr, "[ocl] plan-table arena: chunk %zu allocated (%zu bytes)\n", arena->chunks.size() + 1, cap);
         }
         arena->chunks.push_back(c);
         arena->used = 0;
@@ -755,12 +754,9 @@ int conv_kernels_init() {
     OCL_REQUIRE(dev >= 0 && dev < kMaxDevices, "conv_kernels_init: device %d", dev);
     bool& done = done_dev[dev];
     if (done) return OCL_OK;
-    {
-        const char* e = getenv("OCL_DETERMINISTIC");
-        if (e && e[0] == '1') {
-            int rc = set_deterministic_sums(1);
-            if (rc != OCL_OK) return rc;
-        }
+    if (env_on("OCL_DETERMINISTIC")) {
+        int rc = set_deterministic_sums(1);
+        if (rc != OCL_OK) return rc;
     }
     if (int rc = wgrad_kernels_init()) return rc;
     if (int rc = convw_kernels_init()) return rc;

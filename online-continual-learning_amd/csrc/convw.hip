@@ -1035,7 +1035,7 @@ static int plan_conv_w_mn(const ConvGeomDesc& g, ConvPlan* p, int MT, int NT) {
     a.xf = 0;
     p->cw = 1; p->cs = 0; p->q4 = 0; p->MT = MT; p->NT = NT;
     {   // 2: conv_wx_kernel has an instantiation for this shape (OCL_CONV_WX=0: the generic kernel everywhere -- A/B reference)
-        static const bool env_wx = [] { const char* e = getenv("OCL_CONV_WX"); return !(e && atoi(e) == 0); }();
+        static const bool env_wx = env_int("OCL_CONV_WX", 1) != 0;
         if (env_wx && a.imgs == 1 && a.aligned == 1 && convwx_fn(MT, NT, a.Qpad / 4, a.nstage, 0, 0)) p->cw = 2;
     }
     p->lds_bytes = lds;

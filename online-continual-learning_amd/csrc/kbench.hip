@@ -236,7 +236,7 @@ static void bench_geom(const char* lname, const char* kind, ConvGeomDesc g, cons
                     CK(hipMemcpy(b.data(), stats2, b.size() * sizeof(StatCell), hipMemcpyDeviceToHost));
                     for (int i = 0; i < g.groups * 2 * g.Cout; ++i) {
                         double y = 0;   // (deterministic mode: 2^-40 fixed point in two integer words; default: a double in the first word -- conv.h StatCell)
-                        static const bool det = [] { const char* e = getenv("OCL_DETERMINISTIC"); return e && e[0] == '1'; }();
+                        static const bool det = env_on("OCL_DETERMINISTIC");
                         for (int r = 0; r < kStatReps; ++r) {
                             const StatCell& cell = b[(size_t)r * 8 * 2 * 1024 + i];
                             double dv;
@@ -962,8 +962,8 @@ int main(int argc, char** argv) {
                 }
             }
             WgradPlan wp;
-            const char* wt = getenv("KBENCH_WG_TARGET");   // (the layer's split inside the merged launch of a replay-sized pass: net.hip passes 96)
-            OK(plan_wgrad(N, c.Hin, c.Win, c.CinT, c.Ho, c.Wo, c.Cout, c.k, c.stride, &wp, 0, wt ? atoi(wt) : 0));
+            const int wt = env_int("KBENCH_WG_TARGET", 0);   // (the layer's split inside the merged launch of a replay-sized pass: net.hip passes 96)
+            OK(plan_wgrad(N, c.Hin, c.Win, c.CinT, c.Ho, c.Wo, c.Cout, c.k, c.stride, &wp, 0, wt));
             printf("%-20s wgrad  M=%4d N=%3d K=%7d  MTW=%d NTW=%d grid=%4dx%3d lds=%6zu KC=%3d CP=%3d S=%4d tiles=%d KP=%d q4=%d xcd=%d multi=%d partial=%6.2f MB\n", l.name.c_str(),
                    c.k * c.k * c.CinT, c.Cout, N * c.Ho * c.Wo, wp.MTW, wp.NTW, wp.grid_x, wp.grid_y, wp.lds_bytes, wp.a.KC, wp.a.CP, wp.a.S,
                    wp.a.total_tiles, wp.a.KP, wp.q_rgw, wp.a.xcd_by, wgrad_multi_variant(wp), wp.partial_floats * 4e-6);
@@ -1099,7 +1099,7 @@ int main(int argc, char** argv) {
             const ConvShape& c = l.s;
             WgradPlan wp;
             // (KBENCH_WG_TARGET: the pixel split of a layer inside the merged launch of a replay-sized pass, net.hip: 96)
-            static const int env_wt = [] { const char* e = getenv("KBENCH_WG_TARGET"); return e ? atoi(e) : 0; }();
+            static const int env_wt = env_int("KBENCH_WG_TARGET", 0);
             OK(plan_wgrad(N, c.Hin, c.Win, c.CinT, c.Ho, c.Wo, c.Cout, c.k, c.stride, &wp, 0, env_wt));
             wp.a.x = bufA; wp.a.dy = bufB; wp.a.partial = partial;
             const int nwg = wp.grid_x * wp.grid_y;

@@ -3,6 +3,7 @@
 // :140-168 (SupConResNet) of the reference; parameters stay in PyTorch's named_parameters() order and OIHW layout.
 #include "conv.h"
 #include <chrono>
+#include <limits.h>
 #include <string.h>
 #include <stdlib.h>
 #include <string>
@@ -17,6 +18,7 @@ using namespace ocl;
 namespace {
 
 const int kGmax = 8;  // BN groups per forward (SCR uses 2)
+const int kBnFusedReps = 8;  // replicas of the one-pass BatchNorm backward's accumulators ([rep][2 groups][2][C]; its arrival counters follow them)
 
 struct TensorInfo {
     std::string name;
@@ -148,6 +150,37 @@ struct ocl_net {
     std::map<std::tuple<int, int, const float*>, std::array<WgradMultiTable, 2>> wgrad_tables;
 };
 
+// Every address of one BatchNorm, for the parameter array P, the gradient array Gr (null in a forward) and the tape slot S of a pass.  The
+// only place that knows save_off, kGmax * C, stat_off, arena_off, barena_off and fused_off: the kernel-argument structs are filled from it.
+struct BnView {
+    int C;
+    const float *gamma, *beta;
+    float *dgamma, *dbeta;
+    float *save_mean, *save_invstd;      // [kGmax][C] each, in the slot
+    float *running_mean, *running_var;
+    int64_t* nbt;
+    StatCell* stats;                     // forward: [kStatReps][G][2][C], replica stride stats_rep_stride
+    StatCell* bsums;                     // backward: [set][G][2][C], two BatchNorms sharing dz fit at every G <= kGmax
+    StatCell* fsums;                     // backward, <= 2 groups: the one-pass kernel's replicas / the data-gradient epilogue's sums
+    unsigned* barrier;                   // ... and the arrival counters behind them
+};
+static BnView bn_view(const ocl_net* n, const float* P, float* Gr, float* S, int bn) {
+    const BnInfo& b = n->bns[bn];
+    const int64_t g = n->tensors[b.gamma_t].off, be = n->tensors[b.beta_t].off;
+    BnView v;
+    v.C = b.C;
+    v.gamma = P + g; v.beta = P + be;
+    v.dgamma = Gr ? Gr + g : nullptr; v.dbeta = Gr ? Gr + be : nullptr;
+    v.save_mean = S + b.save_off; v.save_invstd = S + b.save_off + (int64_t)kGmax * b.C;
+    v.running_mean = n->running + b.stat_off; v.running_var = n->running + b.stat_off + b.C;
+    v.nbt = n->nbt + bn;
+    v.stats = n->statsbuf() + b.arena_off;
+    v.bsums = n->bsumsbuf() + b.barena_off;
+    v.fsums = n->bsumsbuf() + b.fused_off;
+    v.barrier = (unsigned*)(v.fsums + (int64_t)kBnFusedReps * 2 * 2 * b.C);
+    return v;
+}
+
 // -----------------------------------------------------------------------------------------------------
 static int add_tensor(ocl_net* n, const std::string& name, std::initializer_list<int64_t> shape) {
     TensorInfo t;
@@ -197,6 +230,8 @@ static int add_conv(ocl_net* n, const std::string& name, int Cin, int Cout, int 
 }
 
 static int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+// the size of a pass of N images, as the thresholds below state it: images x input pixels
+static int64_t in_pixels(const ocl_net* n, int N) { return (int64_t)N * n->d.in_h * n->d.in_w; }
 
 static const int kTwoStreamMinBatch = 48;
 static int build_layout(ocl_net* n) {
@@ -353,7 +388,7 @@ static int build_layout(ocl_net* n) {
     }
     for (auto& b : n->bns) {
         b.fused_off = fo;
-        fo += (int64_t)8 * 2 * 2 * b.C + 8;   // + 9 arrival counters (unsigned)
+        fo += (int64_t)kBnFusedReps * 2 * 2 * b.C + 8;   // + 9 arrival counters (unsigned)
     }
     n->bsums_doubles = fo;
     n->off_bsums = takeb(fo * (int64_t)sizeof(StatCell));
@@ -391,7 +426,7 @@ static int make_plan_set(const ocl_net* n, int N, int groups, PlanSet* out) {
     ps.wgrad_target.assign(n->convs.size(), 0);
     // BatchNorm backward of bn1: its two batch sums in the epilogue of conv2's data gradient (EPI_BNB) + a streaming apply kernel instead
     // of the one-pass kernel with its grid-wide arrival (OCL_BNB_EPI=0: the one-pass kernel).  The replicated arena holds <= 2 groups.
-    static const bool env_bnb = [] { const char* e = getenv("OCL_BNB_EPI"); return !(e && e[0] == '0'); }();
+    static const bool env_bnb = env_not_off("OCL_BNB_EPI");
     for (size_t i = 0; i < n->convs.size(); ++i) {
         const ConvInfo& c = n->convs[i];
         ConvGeomDesc g;
@@ -400,19 +435,18 @@ static int make_plan_set(const ocl_net* n, int N, int groups, PlanSet* out) {
         int rc = plan_conv(g, &ps.fwd[i]);
         if (rc != OCL_OK) return rc;
         if (c.Cin != 3) {
-            // stride-2 3x3: the four parity classes as one launch where conv_t_kernel can take them (else four launches)
-            const bool merge = true;
             std::vector<ConvGeomDesc> dg;
             // (stage 2, passes up to kBnbEpi2MaxPix: the data gradient of conv1 of an identity block completes dL/dz of the block in front
             // of it -- or of the stem -- and carries the reduction half of THAT BatchNorm's backward (bn2 of a block without a projection
             // shortcut, the stem's) the same way; see trunk_backward)
-            const bool size_bnb2 = (int64_t)N * n->d.in_h * n->d.in_w <= kBnbEpi2MaxPix;
+            const bool size_bnb2 = in_pixels(n, N) <= kBnbEpi2MaxPix;
             bool bnb2 = false;
             if (env_bnb && size_bnb2 && c.stride == 1 && groups <= 2)
                 for (size_t k = 0; k < n->blocks.size(); ++k)
                     if (n->blocks[k].conv1 == (int)i && n->blocks[k].convs < 0 && (k == 0 || n->blocks[k - 1].convs < 0)) bnb2 = true;
             const bool bnb = (env_bnb && c.xf_src >= 0 && c.stride == 1 && groups <= 2) || bnb2;   // conv2 of a block: its data gradient enters bn1's backward
-            geom_dgrad(c, N, &dg, merge, bnb ? groups : 1);
+            // stride-2 3x3: the four parity classes as one launch where conv_t_kernel can take them (else four launches)
+            geom_dgrad(c, N, &dg, true, bnb ? groups : 1);
             if (bnb && dg.size() == 1) {
                 dg[0].bnb = 1;
                 ps.dgrad_bnb[i] = 1;
@@ -431,8 +465,8 @@ static int make_plan_set(const ocl_net* n, int N, int groups, PlanSet* out) {
         // (a pass whose weight gradients leave in one launch -- trunk_backward's `defer` -- splits every layer's pixels less)
         // (96 workgroups per layer: the merged launch 111 -> ~70 us, the 20-image pass 746 -> 706 us, ER 0.818 -> 0.779 ms; 192 / 128 / 64 / 48 / 32:
         // 0.790 / 0.790 / 0.785 / 0.786 / 0.801 ms -- profiles/r6_wgrad_multi_target.txt; 0 = split as for a launch of its own)
-        static const int env_mt = [] { const char* e = getenv("OCL_WGRAD_MULTI_TARGET"); return e ? atoi(e) : 96; }();
-        const bool merged = env_mt > 0 && N < kTwoStreamMinBatch && (int64_t)N * n->d.in_h * n->d.in_w < (int64_t)kTwoStreamMinBatch * 1024;
+        static const int env_mt = env_int("OCL_WGRAD_MULTI_TARGET", 96);
+        const bool merged = env_mt > 0 && N < kTwoStreamMinBatch && in_pixels(n, N) < (int64_t)kTwoStreamMinBatch * 1024;
         ps.wgrad_target[i] = merged ? env_mt : 0;
         rc = plan_wgrad(N, c.Hin, c.Win, c.CinT, c.Ho, c.Wo, c.Cout, c.k, c.stride, &ps.wgrad[i], c.xf_src >= 0 ? groups : 0, ps.wgrad_target[i]);
         if (rc != OCL_OK) return rc;
@@ -461,8 +495,6 @@ static int get_plans(ocl_net* n, int N, int groups, PlanSet** out) {
         *out = &it->second;
         return OCL_OK;
     }
-    // OCL_LOG_PLANS=1: one line on stderr per plan set made (host time): what a first-seen batch shape costs a running loop
-    static const bool log_plans = [] { const char* e = getenv("OCL_LOG_PLANS"); return e && e[0] == '1'; }();
     const auto t_plan0 = std::chrono::steady_clock::now();
     struct PlanLog {
         bool on; int N, groups; std::chrono::steady_clock::time_point t0; size_t* count;
@@ -473,7 +505,7 @@ static int get_plans(ocl_net* n, int N, int groups, PlanSet** out) {
     };
     static size_t n_sets = 0;
     ++n_sets;
-    PlanLog plog{log_plans, N, groups, t_plan0, &n_sets};
+    PlanLog plog{log_plans(), N, groups, t_plan0, &n_sets};
     PlanSet ps;
     int rc = make_plan_set(n, N, groups, &ps);
     if (rc != OCL_OK) return rc;
@@ -531,6 +563,12 @@ static int upload_descs(ocl_net* n, hipStream_t s) {
     OCL_HIP(hipStreamSynchronize(s));  // host vectors go out of scope
     n->descs_uploaded = true;
     return OCL_OK;
+}
+// the pack arena now holds the layouts `mask` (PACK_* bits) of the weights in P, written on stream s
+static void note_packed(ocl_net* n, const float* P, int mask, hipStream_t s) {
+    n->pack_src = P;
+    n->pack_have = mask;
+    n->pack_stream = s;
 }
 static const PackDesc* pack_descs(const ocl_net* n) { return (const PackDesc*)(n->ws + n->off_descs); }
 static const BnFoldDesc* fold_descs(const ocl_net* n) {
@@ -632,7 +670,7 @@ static int head_forward(ocl_net* n, const float* P, float* feat, float* h1, floa
 // trailing layers of a large pass's backward handed to the weight-gradient stream one by one (OCL_WGRAD_FLUSH_TAIL; trunk_backward)
 constexpr int kWgradFlushTail = 5;
 // projection shortcut / head weight gradients on the side stream from 96 x 32 x 32 input pixels on (OCL_SIDE_EXTRA_MIN: A/B, profiles/r6_side_extra_ab.txt)
-static const int kSideExtraMinBatch = [] { const char* e = getenv("OCL_SIDE_EXTRA_MIN"); return e ? atoi(e) : 96; }();
+static const int kSideExtraMinBatch = env_int("OCL_SIDE_EXTRA_MIN", 96);
 
 static int ensure_side_stream(ocl_net* n) {
     if (n->s2) return OCL_OK;
@@ -668,18 +706,16 @@ static int side_join(ocl_net* n, hipStream_t s) {
     return OCL_OK;
 }
 
-// kTwoStreamMinBatch x 32 x 32 input pixels: the smallest pass whose weight gradients leave the caller's stream.  Debug stops and
-// measurement runs (ocl_prof_enable, OCL_SINGLE_STREAM=1: per-kernel durations of the kernel alone) stay on one stream.
-static bool two_streams_at(int64_t in_pixels, int dbg_stop) {
-    static const bool env_single = [] { const char* e = getenv("OCL_SINGLE_STREAM"); return e && e[0] == '1'; }();
-    return dbg_stop < 0 && in_pixels >= (int64_t)kTwoStreamMinBatch * 1024 && !prof_on() && !env_single;
+// The one stream predicate: a pass of `pixels` (images x input pixels) gives work to the side stream from min_batch x 32 x 32 on.  Debug
+// stops and measurement runs (ocl_prof_enable, OCL_SINGLE_STREAM=1: per-kernel durations of the kernel alone) stay on one stream.
+static bool side_stream_at(int64_t pixels, int min_batch, int dbg_stop) {
+    static const bool env_single = env_on("OCL_SINGLE_STREAM");
+    return dbg_stop < 0 && pixels >= (int64_t)min_batch * 1024 && !prof_on() && !env_single;
 }
-// ... and the smallest whose head dW / db (and projection shortcuts) go to the side stream
-static bool head_side_at(int64_t in_pixels, bool two_streams) { return two_streams && in_pixels >= (int64_t)kSideExtraMinBatch * 1024; }
-static bool backward_two_streams(const ocl_net* n, int N) { return two_streams_at((int64_t)N * n->d.in_h * n->d.in_w, n->dbg_stop); }
-static bool head_on_side_stream(const ocl_net* n, int N, bool two_streams) {
-    return head_side_at((int64_t)N * n->d.in_h * n->d.in_w, two_streams);
-}
+// kTwoStreamMinBatch: the smallest pass whose weight gradients leave the caller's stream
+static bool two_streams_at(int64_t pixels, int dbg_stop) { return side_stream_at(pixels, kTwoStreamMinBatch, dbg_stop); }
+// ... kSideExtraMinBatch: the smallest whose head dW / db go there as well (and, in the forward, the projection shortcuts)
+static bool head_side_at(int64_t pixels, bool two_streams) { return two_streams && pixels >= (int64_t)kSideExtraMinBatch * 1024; }
 
 // The tensors of the head's backward: the tape of head_forward, the incoming gradient, and where the stage gradients go.
 struct HeadBwd {
@@ -695,7 +731,7 @@ static int head_backward(ocl_net* n, const float* P, float* Gr, const HeadBwd& t
     const int FD = n->feat_dim, OD = n->out_dim;
     auto lin_bwd = [&](const float* dy, int ncol, const float* xin, int kin, int tw, int tb, float* dx) -> int {
         // y = x W^T + b, W [ncol, kin]
-        const bool hs = head_on_side_stream(n, N, two_streams);
+        const bool hs = head_side_at(in_pixels(n, N), two_streams);
         hipStream_t sw = hs ? n->s2 : s;
         int r = hs ? side_wait(n, s) : OCL_OK;   // dy is complete
         if (r) return r;
@@ -731,13 +767,13 @@ static int head_backward(ocl_net* n, const float* P, float* Gr, const HeadBwd& t
 // while profiling (per-kernel events) or under a debug stop.
 // -----------------------------------------------------------------------------------------------------
 static bool graph_enabled(const ocl_net* n) {
-    static const bool env_graph = [] { const char* e = getenv("OCL_GRAPH"); return e && e[0] == '1'; }();
+    static const bool env_graph = env_on("OCL_GRAPH");
     return env_graph && !prof_on() && n->dbg_stop < 0;
 }
 template <class F>
 static int run_replayed(ocl_net* n, ocl_net::GraphKey key, hipStream_t s, F&& body) {
     if (!graph_enabled(n)) return body();
-    static const bool verbose = [] { const char* e = getenv("OCL_GRAPH_VERBOSE"); return e && e[0] == '1'; }();
+    static const bool verbose = env_on("OCL_GRAPH_VERBOSE");
     ocl_net::GraphSlot& g = n->graphs[key];
     if (g.exec) {
         OCL_HIP(hipGraphLaunch(g.exec, s));
@@ -873,6 +909,14 @@ int ocl_net_bind(ocl_net* net, float* params, float* grads, float* running, int6
 
 }  // extern "C"
 
+// the unbound one-slot net of the test hooks (layout, plans and head only; the caller destroys it)
+static int make_test_net(int hw, int nf, int n_classes, int head, int feat_dim, int max_batch, ocl_net** out) {
+    ocl_net_desc d;
+    memset(&d, 0, sizeof(d));
+    d.in_h = d.in_w = hw; d.nf = nf; d.n_classes = n_classes; d.head = head; d.feat_dim = feat_dim; d.max_batch = max_batch; d.n_slots = 1;
+    return ocl_net_create(&d, out);
+}
+
 // -----------------------------------------------------------------------------------------------------
 // Train-mode trunk: images [0, Nc) of the batch as G BatchNorm groups, every launch on `st`.  upd: update the running statistics
 // inside the BatchNorm kernels (once per group, in group order = the reference's separate forward calls).  side: the projection
@@ -884,81 +928,65 @@ int ocl_net_bind(ocl_net* net, float* params, float* grads, float* running, int6
 // OCL_DEBUG_SKIP_SHORTCUT=1: no projection-shortcut convolution, data gradient or weight gradient (the fold into the block's 3x3
 // stride-2 convolution keeps their arithmetic).
 static bool dbg_skip_bn2fwd() {
-    static const bool v = [] { const char* e = getenv("OCL_DEBUG_SKIP_BN2FWD"); return e && e[0] == '1'; }();
+    static const bool v = env_on("OCL_DEBUG_SKIP_BN2FWD");
     return v;
 }
 static bool dbg_skip_shortcut() {
-    static const bool v = [] { const char* e = getenv("OCL_DEBUG_SKIP_SHORTCUT"); return e && e[0] == '1'; }();
+    static const bool v = env_on("OCL_DEBUG_SKIP_SHORTCUT");
     return v;
 }
 
 static int trunk_forward_train(ocl_net* n, PlanSet* ps, const float* P, float* S, int Nc, int G, bool upd, float* feat, hipStream_t st,
                                bool side = false, bool frozen = false, bool fuse = false) {
-    const int img0 = 0, g0 = 0;
     float* pack = (float*)(n->ws + n->off_pack);
-    StatCell* stats = n->statsbuf();
     int rc = OCL_OK;
-    // (cleared by the forward's weight-pack launch)
-    auto at = [&](int64_t off, const ConvInfo& c) { return S + off + (int64_t)img0 * c.Ho * c.Wo * c.Cout; };
+    auto view = [&](int conv_i) { return bn_view(n, P, nullptr, S, n->convs[conv_i].bn); };
     // side: the projection shortcut's 1x1 convolution (3 blocks) runs on the engine's second stream next to conv1 / bn1 / conv2 of its
     // block, which do not depend on it
     // conv_b >= 0: the projection shortcut whose BatchNorm output is this BatchNorm's residual, normalised in the same launch
     auto bn_fwd = [&](int conv_i, const float* y, float* z, const float* res, int relu, hipStream_t st, int conv_b = -1) -> int {
         const ConvInfo& c = n->convs[conv_i];
-        const BnInfo& b = n->bns[c.bn];
+        const BnView v = view(conv_i);
         BnFwdArgs a;
         memset(&a, 0, sizeof(a));
         a.y = y; a.z = z; a.res = res;
-        a.stats = stats + b.arena_off;
+        a.stats = v.stats;   // (cleared by the forward's weight-pack launch)
         a.stat_rep_stride = n->stats_rep_stride;
-        a.gamma = P + n->tensors[b.gamma_t].off;
-        a.beta = P + n->tensors[b.beta_t].off;
-        a.running_mean = upd ? n->running + b.stat_off : nullptr;
-        a.running_var = upd ? n->running + b.stat_off + b.C : nullptr;
-        a.nbt = upd ? n->nbt + c.bn : nullptr;
-        a.save_mean = S + b.save_off + (int64_t)g0 * b.C;
-        a.save_invstd = S + b.save_off + (int64_t)kGmax * b.C + (int64_t)g0 * b.C;
+        a.gamma = v.gamma; a.beta = v.beta;
+        a.running_mean = upd ? v.running_mean : nullptr;
+        a.running_var = upd ? v.running_var : nullptr;
+        a.nbt = upd ? v.nbt : nullptr;
+        a.save_mean = v.save_mean; a.save_invstd = v.save_invstd;
         a.m_per_group = (int64_t)(Nc / G) * c.Ho * c.Wo;
-        a.G = G; a.C = b.C; a.relu = relu;
+        a.G = G; a.C = v.C; a.relu = relu;
         a.momentum = 0.1f; a.eps = 1e-5f;
-        if (frozen) {
-            a.frozen_mean = n->running + b.stat_off;
-            a.frozen_var = n->running + b.stat_off + b.C;
-        }
+        if (frozen) { a.frozen_mean = v.running_mean; a.frozen_var = v.running_var; }
         if (conv_b >= 0) {
-            const ConvInfo& cb = n->convs[conv_b];
-            const BnInfo& bb = n->bns[cb.bn];
-            a.yb = at(cb.y_off, cb);
-            a.stats_b = stats + bb.arena_off;
-            a.gamma_b = P + n->tensors[bb.gamma_t].off;
-            a.beta_b = P + n->tensors[bb.beta_t].off;
-            a.running_mean_b = upd ? n->running + bb.stat_off : nullptr;
-            a.running_var_b = upd ? n->running + bb.stat_off + bb.C : nullptr;
-            a.nbt_b = upd ? n->nbt + cb.bn : nullptr;
-            a.save_mean_b = S + bb.save_off + (int64_t)g0 * bb.C;
-            a.save_invstd_b = S + bb.save_off + (int64_t)kGmax * bb.C + (int64_t)g0 * bb.C;
-            if (frozen) {
-                a.frozen_mean_b = n->running + bb.stat_off;
-                a.frozen_var_b = n->running + bb.stat_off + bb.C;
-            }
+            const BnView w = view(conv_b);
+            a.yb = S + n->convs[conv_b].y_off;
+            a.stats_b = w.stats;
+            a.gamma_b = w.gamma; a.beta_b = w.beta;
+            a.running_mean_b = upd ? w.running_mean : nullptr;
+            a.running_var_b = upd ? w.running_var : nullptr;
+            a.nbt_b = upd ? w.nbt : nullptr;
+            a.save_mean_b = w.save_mean; a.save_invstd_b = w.save_invstd;
+            if (frozen) { a.frozen_mean_b = w.running_mean; a.frozen_var_b = w.running_var; }
         }
         return launch_bn_fwd(a, st);
     };
-    auto conv_stats = [&](int conv_i, const float* in, hipStream_t st) -> int {
+    auto conv_stats = [&](int conv_i, const float* in, hipStream_t st, const XfBn* xf = nullptr) -> int {
         const ConvInfo& c = n->convs[conv_i];
-        return run_conv(n, ps->fwd[conv_i], in, pack + c.tf_off, at(c.y_off, c), EPI_STATS, stats + n->bns[c.bn].arena_off, nullptr,
-                        nullptr, nullptr, nullptr, st);
+        return run_conv(n, ps->fwd[conv_i], in, pack + c.tf_off, S + c.y_off, EPI_STATS, view(conv_i).stats, nullptr, nullptr, nullptr, nullptr, st, xf);
     };
     const ConvInfo& c0 = n->convs[0];
-    const float* x4 = S + n->x4_off + (int64_t)img0 * n->d.in_h * n->d.in_w * 4;
-    if ((rc = conv_stats(0, x4, st))) return rc;
-    float* cur = at(n->zstem_off, c0);
-    if ((rc = bn_fwd(0, at(c0.y_off, c0), cur, nullptr, 1, st))) return rc;
+    if ((rc = conv_stats(0, S + n->x4_off, st))) return rc;
+    float* cur = S + n->zstem_off;
+    if ((rc = bn_fwd(0, S + c0.y_off, cur, nullptr, 1, st))) return rc;
     for (auto& b : n->blocks) {
         const ConvInfo& c1 = n->convs[b.conv1];
         const ConvInfo& c2 = n->convs[b.conv2];
-        float* a1 = at(b.a1_off, c1);
-        float* z = at(b.z_off, c2);
+        float* a1 = S + b.a1_off;
+        float* z = S + b.z_off;
         const float* res = cur;
         if (b.convs >= 0) {
             hipStream_t ss = side ? n->s2 : st;
@@ -971,30 +999,60 @@ static int trunk_forward_train(ocl_net* n, PlanSet* ps, const float* P, float* S
         if (fuse) {
             // relu(bn1(.)) is applied by conv2 while it stages its patches: no BatchNorm launch, a1 is never written (the backward
             // recomputes it where it needs it: weight gradient of conv2, ReLU mask of bn1's backward)
-            const BnInfo& b1 = n->bns[c1.bn];
+            const BnView v = view(b.conv1);
             XfBn xf;
-            xf.stats = stats + b1.arena_off;
-            xf.gamma = P + n->tensors[b1.gamma_t].off;
-            xf.beta = P + n->tensors[b1.beta_t].off;
-            xf.save_mean = S + b1.save_off;
-            xf.save_invstd = S + b1.save_off + (int64_t)kGmax * b1.C;
-            xf.running_mean = upd ? n->running + b1.stat_off : nullptr;
-            xf.running_var = upd ? n->running + b1.stat_off + b1.C : nullptr;
-            xf.nbt = upd ? n->nbt + c1.bn : nullptr;
+            xf.stats = v.stats;
+            xf.gamma = v.gamma; xf.beta = v.beta;
+            xf.save_mean = v.save_mean; xf.save_invstd = v.save_invstd;
+            xf.running_mean = upd ? v.running_mean : nullptr;
+            xf.running_var = upd ? v.running_var : nullptr;
+            xf.nbt = upd ? v.nbt : nullptr;
             xf.m_per_group = (int64_t)(Nc / G) * c1.Ho * c1.Wo;
-            if ((rc = run_conv(n, ps->fwd[b.conv2], at(c1.y_off, c1), pack + c2.tf_off, at(c2.y_off, c2), EPI_STATS,
-                               stats + n->bns[c2.bn].arena_off, nullptr, nullptr, nullptr, nullptr, st, &xf)))
-                return rc;
+            if ((rc = conv_stats(b.conv2, S + c1.y_off, st, &xf))) return rc;
         } else {
-            if ((rc = bn_fwd(b.conv1, at(c1.y_off, c1), a1, nullptr, 1, st))) return rc;
+            if ((rc = bn_fwd(b.conv1, S + c1.y_off, a1, nullptr, 1, st))) return rc;
             if ((rc = conv_stats(b.conv2, a1, st))) return rc;
         }
         if (b.convs >= 0 && side && (rc = side_join(n, st))) return rc;
-        if (!(dbg_skip_bn2fwd() && &b != &n->blocks.back()) && (rc = bn_fwd(b.conv2, at(c2.y_off, c2), z, res, 1, st, b.convs))) return rc;
+        if (!(dbg_skip_bn2fwd() && &b != &n->blocks.back()) && (rc = bn_fwd(b.conv2, S + c2.y_off, z, res, 1, st, b.convs))) return rc;
         cur = z;
     }
     if (!feat) return OCL_OK;   // (a pass run for its running-statistic updates alone)
     return launch_avgpool_fwd(cur, feat, Nc, n->Hf, n->Wf, n->convs[n->blocks.back().conv2].Cout, st);
+}
+
+// Eval-mode trunk: every BatchNorm folded to a scale and a shift (from the running statistics) that its convolution's epilogue applies; no
+// tape, the activations rotate through four scratch buffers.  `ps` may be planned for more than N images (ocl_net_forward_segments).
+static int trunk_forward_eval(ocl_net* n, PlanSet* ps, const float* P, const float* x4, int N, float* feat, hipStream_t s) {
+    float* pack = (float*)(n->ws + n->off_pack);
+    float* fold = (float*)(n->ws + n->off_fold);   // scale[C], shift[C] per BatchNorm, laid out like the running statistics
+    int rc = launch_bn_fold(P, n->running, fold, fold_descs(n), (int)n->bns.size(), 1e-5f, s);
+    if (rc) return rc;
+    auto conv_eval = [&](int conv_i, const float* in, float* o, const float* res, int relu) -> int {
+        const ConvInfo& c = n->convs[conv_i];
+        const BnInfo& b = n->bns[c.bn];
+        int fl = EPI_AFFINE | (res ? EPI_RES : 0) | (relu ? EPI_RELU : 0);
+        return run_conv(n, ps->fwd[conv_i], in, pack + c.tf_off, o, fl, nullptr, fold + b.stat_off, fold + b.stat_off + b.C, res, nullptr, s);
+    };
+    float* bufs[4] = {n->gbuf(0), n->gbuf(1), n->gbuf(2), n->gbuf(3)};
+    float* cur = bufs[0];
+    if ((rc = conv_eval(0, x4, cur, nullptr, 1))) return rc;
+    int ci = 0;
+    for (auto& b : n->blocks) {
+        float* a1 = bufs[(ci + 1) & 3];
+        float* sc = bufs[(ci + 2) & 3];
+        float* z = bufs[(ci + 3) & 3];
+        if ((rc = conv_eval(b.conv1, cur, a1, nullptr, 1))) return rc;
+        const float* res = cur;
+        if (b.convs >= 0) {
+            if ((rc = conv_eval(b.convs, cur, sc, nullptr, 0))) return rc;
+            res = sc;
+        }
+        if ((rc = conv_eval(b.conv2, a1, z, res, 1))) return rc;
+        cur = z;
+        ci = (ci + 3) & 3;
+    }
+    return launch_avgpool_fwd(cur, feat, N, n->Hf, n->Wf, n->convs[n->blocks.back().conv2].Cout, s);
 }
 
 extern "C" {
@@ -1067,10 +1125,8 @@ int ocl_net_forward_segments(ocl_net* n, const float* const* xs, const int32_t* 
     const bool feat_direct = feat_out && !out && !(flags & OCL_FWD_SAVE_TAPE) && !replay;
     float* feat = feat_direct ? feat_out : S + n->feat_off;
     const bool upd = (flags & OCL_FWD_UPDATE_RUNNING) != 0;
-    static const bool env_single = [] { const char* e = getenv("OCL_SINGLE_STREAM"); return e && e[0] == '1'; }();
     // (threshold in images x input pixels: MIR's 50-image 84 x 84 passes qualify, 5.05 -> 4.99 ms per step)
-    const bool side_big = (int64_t)N * n->d.in_h * n->d.in_w >= (int64_t)kSideExtraMinBatch * 1024;
-    const bool side = train && n->dbg_stop < 0 && side_big && !prof_on() && !env_single;
+    const bool side = train && side_stream_at(in_pixels(n, N), kSideExtraMinBatch, n->dbg_stop);
     if (side && (rc = ensure_side_stream(n))) return rc;
     const bool fused = train && !frozen;
     const bool want_head = out || (flags & OCL_FWD_SAVE_TAPE);
@@ -1090,38 +1146,9 @@ int ocl_net_forward_segments(ocl_net* n, const float* const* xs, const int32_t* 
                                                  n->off_bsums + n->bsums_doubles * (int64_t)sizeof(StatCell));
             OCL_HIP(hipMemsetAsync(lo, 0, (size_t)(hi - lo), s));
         }
-        if (train) {
-            if ((rc = trunk_forward_train(n, ps, P, S, N, groups, upd && !frozen, (feat_out || want_head) ? feat : nullptr, s, side, frozen, fused))) return rc;
-        } else {
-            float* fold = (float*)(n->ws + n->off_fold);
-            if ((rc = launch_bn_fold(P, n->running, fold, fold_descs(n), (int)n->bns.size(), 1e-5f, s))) return rc;
-            auto conv_eval = [&](int conv_i, const float* in, float* o, const float* res, int relu) -> int {
-                const ConvInfo& c = n->convs[conv_i];
-                const BnInfo& b = n->bns[c.bn];
-                int fl = EPI_AFFINE | (res ? EPI_RES : 0) | (relu ? EPI_RELU : 0);
-                return run_conv(n, ps->fwd[conv_i], in, pack + c.tf_off, o, fl, nullptr, fold + b.stat_off, fold + b.stat_off + b.C, res,
-                                nullptr, s);
-            };
-            float* bufs[4] = {n->gbuf(0), n->gbuf(1), n->gbuf(2), n->gbuf(3)};
-            float* cur = bufs[0];
-            if ((rc = conv_eval(0, x4, cur, nullptr, 1))) return rc;
-            int ci = 0;
-            for (auto& b : n->blocks) {
-                float* a1 = bufs[(ci + 1) & 3];
-                float* sc = bufs[(ci + 2) & 3];
-                float* z = bufs[(ci + 3) & 3];
-                if ((rc = conv_eval(b.conv1, cur, a1, nullptr, 1))) return rc;
-                const float* res = cur;
-                if (b.convs >= 0) {
-                    if ((rc = conv_eval(b.convs, cur, sc, nullptr, 0))) return rc;
-                    res = sc;
-                }
-                if ((rc = conv_eval(b.conv2, a1, z, res, 1))) return rc;
-                cur = z;
-                ci = (ci + 3) & 3;
-            }
-            if ((rc = launch_avgpool_fwd(cur, feat, N, n->Hf, n->Wf, n->convs[n->blocks.back().conv2].Cout, s))) return rc;
-        }
+        rc = train ? trunk_forward_train(n, ps, P, S, N, groups, upd && !frozen, (feat_out || want_head) ? feat : nullptr, s, side, frozen, fused)
+                   : trunk_forward_eval(n, ps, P, x4, N, feat, s);
+        if (rc != OCL_OK) return rc;
         if (want_head && (rc = head_forward(n, P, feat, S + n->h1_off, S + n->h2_off, S + n->norms_off, S + n->out_off, N, s, head_out2, &wrote)))
             return rc;
         return OCL_OK;
@@ -1139,11 +1166,7 @@ int ocl_net_forward_segments(ocl_net* n, const float* const* xs, const int32_t* 
     // A pack launch wrote exactly `pack_mask` from the array's CURRENT contents; whatever else the arena held for the same pointer may be
     // from before an optimiser step and counts as gone (round 5: with OCL_FWD_SAME_WEIGHTS a stale data-gradient pack would otherwise
     // be trusted by the next taped forward -- the bug tests/test_gpu_net.py::test_same_weights_... now pins)
-    if (!same_weights) {
-        n->pack_have = pack_mask;
-        n->pack_stream = s;
-        n->pack_src = P;
-    }
+    if (!same_weights) note_packed(n, P, pack_mask, s);
     if (rc != OCL_OK) return rc;
     if (train) {
         n->slot_fused[slot] = fused;
@@ -1170,16 +1193,14 @@ int ocl_net_forward_segments(ocl_net* n, const float* const* xs, const int32_t* 
 // -----------------------------------------------------------------------------------------------------
 static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, float* S, int Nc, int G, int accumulate, const float* dfeat,
                           hipStream_t s, hipStream_t side, bool frozen = false, bool fused = false) {
-    const int img0 = 0, g0 = 0;
     float* pack = (float*)(n->ws + n->off_pack);
     float* partial = n->partialbuf();
-    StatCell* bsums = n->bsumsbuf();
     int rc = OCL_OK;
-    if (!n->bsums_clean) OCL_HIP(hipMemsetAsync(bsums, 0, n->bsums_doubles * sizeof(StatCell), s));   // a second backward since the last forward
+    if (!n->bsums_clean) OCL_HIP(hipMemsetAsync(n->bsumsbuf(), 0, n->bsums_doubles * sizeof(StatCell), s));   // a second backward since the last forward
     n->bsums_clean = false;
-    auto T = [&](int t) { return P + n->tensors[t].off; };
     auto GT = [&](int t) { return Gr + n->tensors[t].off; };
-    auto at = [&](int64_t off, const ConvInfo& c) { return S + off + (int64_t)img0 * c.Ho * c.Wo * c.Cout; };
+    auto view = [&](int conv_i) { return bn_view(n, P, Gr, S, n->convs[conv_i].bn); };
+    const float* x4 = S + n->x4_off;
     float* gA = n->gbuf(0);  // grad wrt current block output
     float* gD = n->gbuf(3);
     float* gE = n->gbuf(4);
@@ -1199,42 +1220,40 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
     const bool batched = Nc < kTwoStreamMinBatch && ps->batched_reduce && n->dbg_stop < 0;
     // ... and on one stream the weight gradients themselves wait for the end: every dL/dy stays in its own buffer, and the layers leave in
     // one launch per form set (conv_wgrad_multi_kernel) in front of the one reduction: 20 launches of the dependent chain -> 1 or 2
-    static const bool env_multi = [] { const char* e = getenv("OCL_WGRAD_MULTI"); return !e || e[0] != '0'; }();
+    static const bool env_multi = env_not_off("OCL_WGRAD_MULTI");
     int n_dy = 1;
     for (auto& b : n->blocks) n_dy += b.convs >= 0 ? 3 : 2;
     const bool defer = env_multi && batched && !two_streams && !n->capturing && n_dy <= ocl_net::kDyKeep;
     // Two streams: with one dL/dy buffer per layer as well, the dependent chain never waits for the weight-gradient stream to hand a ring
     // slot back (and records no event per layer for it) -- OCL_DY_KEEP=0: the ring of kDyRing buffers
-    static const bool env_keep = [] { const char* e = getenv("OCL_DY_KEEP"); return !e || e[0] != '0'; }();
+    static const bool env_keep = env_not_off("OCL_DY_KEEP");
     const bool keep = defer || (env_keep && two_streams && n_dy <= ocl_net::kDyKeep);
     // ... and the weight-gradient stream is told about new dL/dy buffers every OCL_WGRAD_FLUSH layers (an event record on the chain's stream +
     // a wait on the other per hand-over): it lags behind the chain anyway
     // (SCR's 220 views: ring 2.025 ms, per-layer buffers 2.005, + hand-over every 2 / 3 / 5 / 10 / 21 layers 2.000 / 1.990 / 2.054 / 2.109 /
     // 2.256 -- the sooner the other stream has work, the more of it hides; MIR's 50 - 60-image passes: 4.614 / 4.545 / 4.603 at 3:
     // profiles/r6_dy_keep_flush_ab.txt.  Three layers per hand-over from 128 images on.)
-    static const int env_flush = [] { const char* e = getenv("OCL_WGRAD_FLUSH"); return e ? std::max(1, atoi(e)) : 0; }();
-    const int flush_every = env_flush > 0 ? env_flush : (Nc >= 128 ? 3 : 1);
+    static const int env_flush = env_int("OCL_WGRAD_FLUSH", INT_MIN);   // (INT_MIN: unset)
+    const int flush_every = env_flush != INT_MIN ? std::max(1, env_flush) : (Nc >= 128 ? 3 : 1);
     const bool coarse = two_streams && keep && flush_every > 1;
     // ... except at the end of the backward, where the chain is short of what the other stream still has to do: the last
     // OCL_WGRAD_FLUSH_TAIL layers (in backward order; the stem, which stays on the caller's stream, is the last of them) are handed over
     // one by one, each as soon as its dL/dy exists, and the last hand-over is issued in front of the stem's BatchNorm backward instead
     // of behind it.  0: groups of flush_every to the end, the last one behind the stem's BatchNorm backward.
-    static const int env_tail = [] { const char* e = getenv("OCL_WGRAD_FLUSH_TAIL"); return e ? std::max(0, atoi(e)) : kWgradFlushTail; }();
+    static const int env_tail = std::max(0, env_int("OCL_WGRAD_FLUSH_TAIL", kWgradFlushTail));
     const int tail_from = coarse ? n_dy - env_tail : n_dy;   // first layer, in backward order, that is handed over on its own
     int n_handed = 0;
     std::vector<WgradPlan> deferred;
-    auto take_dy = [&](int* slot_out) -> float* {   // next ring slot; the main stream waits for its previous readers
-        if (keep) {
-            *slot_out = n->dy_next;
-            return n->dykeep(n->dy_next++);
-        }
+    // next dL/dy buffer: the layer's own, or the next ring slot (*slot_out, for release; the main stream waits for its previous readers)
+    auto take_dy = [&](int* slot_out = nullptr) -> float* {
+        if (keep) return n->dykeep(n->dy_next++);
         const int r = n->dy_next;
         n->dy_next = (r + 1) % ocl_net::kDyRing;
         if (two_streams && n->ev_done_pending[r]) {
             (void)hipStreamWaitEvent(s, n->ev_done[r], 0);
             n->ev_done_pending[r] = false;
         }
-        *slot_out = r;
+        if (slot_out) *slot_out = r;
         return n->dybuf(r);
     };
     auto publish = [&]() -> int {   // everything the main stream has written so far is visible to the wgrad stream
@@ -1260,24 +1279,21 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
         const int cs[2] = {conv_a, conv_b};
         float* dys[2] = {dya, dyb};
         for (int k = 0; k < a.nsets; ++k) {
-            const ConvInfo& c = n->convs[cs[k]];
-            const BnInfo& b = n->bns[c.bn];
-            a.y[k] = at(c.y_off, c);
-            a.mean[k] = S + b.save_off + (int64_t)g0 * b.C;
-            a.invstd[k] = S + b.save_off + (int64_t)kGmax * b.C + (int64_t)g0 * b.C;
-            a.gamma[k] = T(b.gamma_t);
-            a.beta[k] = T(b.beta_t);
+            const BnView v = view(cs[k]);
+            a.y[k] = S + n->convs[cs[k]].y_off;
+            a.mean[k] = v.save_mean; a.invstd[k] = v.save_invstd;
+            a.gamma[k] = v.gamma; a.beta[k] = v.beta;
             a.dy[k] = dys[k];
-            a.dgamma[k] = GT(b.gamma_t);
-            a.dbeta[k] = GT(b.beta_t);
+            a.dgamma[k] = v.dgamma; a.dbeta[k] = v.dbeta;
         }
         // sums are addressed [set][G][2][C] inside conv_a's arena of 2*kGmax*2*C cells: two sets fit at every G <= kGmax
-        a.sums = bsums + n->bns[ca.bn].barena_off;
+        const BnView va = view(conv_a);
+        a.sums = va.bsums;
         // one-pass kernel (<= 2 groups; two BatchNorms sharing dz each bring their own accumulator arena)
         if (G <= 2) {
-            a.fsums = bsums + n->bns[ca.bn].fused_off;
-            a.barrier = (unsigned*)(a.fsums + (int64_t)8 * 2 * 2 * ca.Cout);
-            if (conv_b >= 0) a.fsums_b = bsums + n->bns[n->convs[conv_b].bn].fused_off;
+            a.fsums = va.fsums;
+            a.barrier = va.barrier;
+            if (conv_b >= 0) a.fsums_b = view(conv_b).fsums;
         }
         a.accumulate = accumulate;
         a.frozen = frozen ? 1 : 0;
@@ -1295,7 +1311,12 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
     // xf_conv >= 0: xin is the RAW output of that convolution; its BatchNorm + ReLU is applied while the kernel stages its patches
     // measurement only (OCL_DEBUG_SKIP_WGRAD=1: the gradients of the convolution weights are NOT computed): the wall time of the dependent
     // chain alone; step time - that = the weight-gradient time the second stream does not hide (bench.py --exposed-wgrad)
-    static const bool env_skip_wgrad = [] { const char* e = getenv("OCL_DEBUG_SKIP_WGRAD"); return e && e[0] == '1'; }();
+    static const bool env_skip_wgrad = env_on("OCL_DEBUG_SKIP_WGRAD");
+    auto flush_reduce = [&](hipStream_t st) -> int {   // one launch reduces the slabs of the layers gathered in `rm`
+        const int r = rm.n > 0 ? launch_wgrad_reduce_multi(rm, st) : OCL_OK;
+        if (!r) rm.n = 0;
+        return r;
+    };
     struct PendingWgrad { int conv_i; const float* xin; const float* dy; int xf_conv; };
     std::vector<PendingWgrad> pending;
     auto wgrad_now = [&](int conv_i, const float* xin, const float* dy, int xf_conv = -1) -> int {   // on the weight-gradient stream
@@ -1304,19 +1325,16 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
         wp.a.x = xin;
         wp.a.dy = dy;
         if (xf_conv >= 0) {
-            const BnInfo& b1 = n->bns[n->convs[xf_conv].bn];
+            const BnView v = view(xf_conv);
             wp.a.xf = 1;
             wp.a.xf_groups = G;
             wp.a.xf_group_size = Nc / G;
-            wp.a.xf_mean = S + b1.save_off;
-            wp.a.xf_invstd = S + b1.save_off + (int64_t)kGmax * b1.C;
-            wp.a.xf_gamma = T(b1.gamma_t);
-            wp.a.xf_beta = T(b1.beta_t);
+            wp.a.xf_mean = v.save_mean; wp.a.xf_invstd = v.save_invstd;
+            wp.a.xf_gamma = v.gamma; wp.a.xf_beta = v.beta;
         }
         if (grouped) {   // slab regions of kGroupRegion bytes side by side, one reduction launch per group_k layers
             if ((int64_t)wp.partial_floats * 4 > kGroupRegion || rm.n >= group_k) {
-                if (rm.n > 0 && (rc = launch_wgrad_reduce_multi(rm, sw))) return rc;
-                rm.n = 0;
+                if ((rc = flush_reduce(sw))) return rc;
             }
             if ((int64_t)wp.partial_floats * 4 <= kGroupRegion) {
                 const int64_t off = (int64_t)rm.n * (kGroupRegion / 4);
@@ -1366,34 +1384,29 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
     // BatchNorm `bn_conv`'s backward with the reduction half in the epilogue of the data gradient that produces d (EPI_BNB): the
     // descriptor for that launch, and the apply launch that follows it
     auto bnb_desc = [&](int bn_conv, const float* zmask) -> BnbEpi {
-        const ConvInfo& c = n->convs[bn_conv];
-        const BnInfo& b = n->bns[c.bn];
+        const BnView v = view(bn_conv);
         BnbEpi e;
-        e.y = at(c.y_off, c);
+        e.y = S + n->convs[bn_conv].y_off;
         e.z = zmask;
-        e.mean = S + b.save_off;
-        e.invstd = S + b.save_off + (int64_t)kGmax * b.C;
-        e.gamma = T(b.gamma_t);
-        e.beta = T(b.beta_t);
-        e.sums = bsums + b.fused_off;
-        e.rep_stride = (int64_t)G * 2 * b.C;
+        e.mean = v.save_mean; e.invstd = v.save_invstd;
+        e.gamma = v.gamma; e.beta = v.beta;
+        e.sums = v.fsums;
+        e.rep_stride = (int64_t)G * 2 * v.C;
         return e;
     };
     auto bn_apply_e = [&](int bn_conv, const float* d, float* dy) -> int {
         const ConvInfo& c = n->convs[bn_conv];
-        const BnInfo& b = n->bns[c.bn];
+        const BnView v = view(bn_conv);
         BnApplyEArgs a;
         memset(&a, 0, sizeof(a));
-        a.d = d; a.y = at(c.y_off, c); a.dy = dy;
-        a.mean = S + b.save_off;
-        a.invstd = S + b.save_off + (int64_t)kGmax * b.C;
-        a.gamma = T(b.gamma_t);
-        a.dgamma = GT(b.gamma_t);
-        a.dbeta = GT(b.beta_t);
-        a.esums = bsums + b.fused_off;
-        a.esums_rep_stride = (int64_t)G * 2 * b.C;
+        a.d = d; a.y = S + c.y_off; a.dy = dy;
+        a.mean = v.save_mean; a.invstd = v.save_invstd;
+        a.gamma = v.gamma;
+        a.dgamma = v.dgamma; a.dbeta = v.dbeta;
+        a.esums = v.fsums;
+        a.esums_rep_stride = (int64_t)G * 2 * v.C;
         a.m_per_group = (int64_t)(Nc / G) * c.Ho * c.Wo;
-        a.G = G; a.C = b.C; a.accumulate = accumulate;
+        a.G = G; a.C = v.C; a.accumulate = accumulate;
         return launch_bn_apply_e(a, s);
     };
 
@@ -1404,16 +1417,14 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
     };
     if (stop_here(99, 0)) return OCL_OK;   // right after the head: gA = dL/dz of the last block
     bool prev_epi = false;   // gA is already ReLU-masked and the batch sums of the BatchNorm it enters are in that BatchNorm's arena
-    const ConvInfo& c0 = n->convs[0];
     for (int bi = (int)n->blocks.size() - 1; bi >= 0; --bi) {
         const BlockInfo& b = n->blocks[bi];
         const ConvInfo& c1 = n->convs[b.conv1];
-        const ConvInfo& c2 = n->convs[b.conv2];
-        const float* xin = bi == 0 ? at(n->zstem_off, c0) : at(n->blocks[bi - 1].z_off, n->convs[n->blocks[bi - 1].conv2]);
-        const float* a1 = at(b.a1_off, c1);
-        const float* z = at(b.z_off, c2);
+        const float* xin = S + (bi == 0 ? n->zstem_off : n->blocks[bi - 1].z_off);
+        const float* a1 = S + b.a1_off;
+        const float* z = S + b.z_off;
         // gA = dL/dz.  bn2 (and the projection BN) share the ReLU-masked gradient.
-        int rB, rC = -1;
+        int rB = -1, rC = -1;
         gB = take_dy(&rB);
         if (b.convs >= 0) gC = take_dy(&rC);
         if (prev_epi) {   // gA arrived masked, bn2's batch sums with it (epilogue of the block behind): the streaming apply kernel
@@ -1426,7 +1437,7 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
             if (!dbg_skip_shortcut() && (rc = wgrad(b.convs, xin, gC))) return rc;
             if ((rc = release(rC))) return rc;                               // (the shortcut's dgrad below reads gC on `s`)
         }
-        if ((rc = fused ? wgrad(b.conv2, at(c1.y_off, c1), gB, b.conv1) : wgrad(b.conv2, a1, gB))) return rc;
+        if ((rc = fused ? wgrad(b.conv2, S + c1.y_off, gB, b.conv1) : wgrad(b.conv2, a1, gB))) return rc;
         if ((rc = release(rB))) return rc;
         // bn1's backward: its batch sums come out of conv2's data gradient (gD = the MASKED dL/da1), a streaming kernel applies them;
         // otherwise (plan without the epilogue table, eval-mode tape, > 2 groups) the one-pass kernel on the unmasked gD
@@ -1435,7 +1446,7 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
         if (epi1) be1 = bnb_desc(b.conv1, fused ? nullptr : a1);
         if ((rc = dgrad(b.conv2, gB, gD, nullptr, nullptr, 0, epi1 ? &be1 : nullptr))) return rc;   // gD = dL/da1 (pre-mask; masked with EPI_BNB)
         if (stop_here(bi, 2)) return OCL_OK;
-        int rB1;
+        int rB1 = -1;
         float* gB1 = take_dy(&rB1);
         if (epi1) {
             if ((rc = bn_apply_e(b.conv1, gD, gB1))) return rc;                                       // gB1 = dL/dy1
@@ -1464,34 +1475,28 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
     }
     // stem
     if (env_tail > 0 && (rc = flush_pending())) return rc;   // (layer1.0.conv1's dL/dy exists: the stem's BatchNorm backward is not waited for)
-    int rS;
-    float* gS = take_dy(&rS);
+    float* gS = take_dy();
     if (prev_epi) {
         if ((rc = bn_apply_e(0, gA, gS))) return rc;
-    } else if ((rc = bn_bwd(gA, at(n->zstem_off, c0), 0, gS, -1, nullptr))) return rc;
+    } else if ((rc = bn_bwd(gA, S + n->zstem_off, 0, gS, -1, nullptr))) return rc;
+    if ((rc = flush_pending())) return rc;
+    bool joined = !two_streams;   // nothing is left on the side stream
+    auto join_side = [&]() -> int {   // the caller's stream waits for all of the side stream, and has whatever weight gradient still follows
+        OCL_HIP(hipEventRecord(n->ev_join, sw));
+        OCL_HIP(hipStreamWaitEvent(s, n->ev_join, 0));
+        for (int i = 0; i < ocl_net::kDyRing; ++i) n->ev_done_pending[i] = false;   // covered by the join
+        sw = s;
+        joined = true;
+        return OCL_OK;
+    };
     // The stem's weight gradient is the tail of the backward: it runs on the caller's stream (no two more cross-stream hand-offs, ~30 us
     // of event latency in the trace) BESIDE the side stream's last kernels -- layer 1's weight gradients, the largest of the step, are
     // still running there when the chain ends -- with its own slab region (the slabs of one layer stay under 12 MB; the stem's start
     // 16 MB into the buffer), and the join follows it.
-    (void)rS;
-    if ((rc = flush_pending())) return rc;
-    if (two_streams && batched) {   // replay-sized pass: the stem's weight gradient and the one reduction of all layers on the side stream, then the join
-        if ((rc = publish())) return rc;
-        if ((rc = wgrad(0, S + n->x4_off + (int64_t)img0 * n->d.in_h * n->d.in_w * 4, gS))) return rc;
-        if ((rc = flush_pending())) return rc;
-        if (rm.n > 0 && (rc = launch_wgrad_reduce_multi(rm, sw))) return rc;
-        OCL_HIP(hipEventRecord(n->ev_join, sw));
-        OCL_HIP(hipStreamWaitEvent(s, n->ev_join, 0));
-        for (int i = 0; i < ocl_net::kDyRing; ++i) n->ev_done_pending[i] = false;   // covered by the join
-        return OCL_OK;
-    }
-    if (two_streams) {
-        if (grouped && rm.n > 0) {   // the layers still waiting for their reduction
-            if ((rc = launch_wgrad_reduce_multi(rm, sw))) return rc;
-            rm.n = 0;
-        }
+    if (two_streams && !batched) {
+        if ((rc = flush_reduce(sw))) return rc;   // the layers still waiting for their reduction
         WgradPlan wp = ps->wgrad[0];
-        wp.a.x = S + n->x4_off + (int64_t)img0 * n->d.in_h * n->d.in_w * 4;
+        wp.a.x = x4;
         wp.a.dy = gS;
         wp.a.partial = partial + stem_region / 4;
         if (stem_region / 4 + (int64_t)wp.partial_floats > n->partial_floats) wp.a.partial = nullptr;   // (workspace too small: after the join)
@@ -1503,15 +1508,16 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
             if ((rc = launch_wgrad(wp, s))) return rc;
             if ((rc = launch_wgrad_reduce(wp, GT(n->convs[0].w_t), accumulate, s))) return rc;
         }
-        OCL_HIP(hipEventRecord(n->ev_join, sw));
-        OCL_HIP(hipStreamWaitEvent(s, n->ev_join, 0));
-        for (int i = 0; i < ocl_net::kDyRing; ++i) n->ev_done_pending[i] = false;   // covered by the join
-        sw = s;
+        if ((rc = join_side())) return rc;
         if (wp.a.partial) return OCL_OK;
     }
-    if ((rc = wgrad(0, S + n->x4_off + (int64_t)img0 * n->d.in_h * n->d.in_w * 4, gS))) return rc;
+    // Every other pass: the stem's weight gradient goes where the other layers' went -- the caller's stream, or the side stream of a replay-sized
+    // pass (the one reduction of all layers there too, then the join) -- followed by what waited for the end of the backward
+    if (!joined && (rc = publish())) return rc;
+    if ((rc = wgrad(0, x4, gS))) return rc;
+    if (!joined && (rc = flush_pending())) return rc;
     if (defer) {   // every layer's weight gradient: one launch per form set, the layers without a form in the merged kernel on their own
-        auto& tabs = n->wgrad_tables[std::make_tuple(Nc, G, (const float*)(S + (int64_t)img0))];
+        auto& tabs = n->wgrad_tables[std::make_tuple(Nc, G, (const float*)S)];
         for (int set = 0; set < 2; ++set) {
             std::vector<WgradPlan> grp;
             for (auto& wp : deferred)
@@ -1523,8 +1529,8 @@ static int trunk_backward(ocl_net* n, PlanSet* ps, const float* P, float* Gr, fl
         for (auto& wp : deferred)
             if (wgrad_multi_variant(wp) < 0 && (rc = launch_wgrad(wp, s))) return rc;
     }
-    if ((batched || grouped) && rm.n > 0 && (rc = launch_wgrad_reduce_multi(rm, s))) return rc;
-    return OCL_OK;
+    if ((rc = flush_reduce(sw))) return rc;
+    return joined ? OCL_OK : join_side();
 }
 
 extern "C" {
@@ -1573,7 +1579,7 @@ int ocl_net_backward(ocl_net* n, int slot, const float* dout, int accumulate, vo
     // trunk come from a ring, a slot is rewritten only after the event behind its last weight-gradient reader.  Replay batches of
     // 10-20 images are latency-bound: the event traffic costs more than the overlap returns there.  Debug stops and measurement
     // runs (ocl_prof_enable, OCL_SINGLE_STREAM=1: per-kernel durations of the kernel alone) stay on one stream as well.
-    const bool two_streams = backward_two_streams(n, N);
+    const bool two_streams = two_streams_at(in_pixels(n, N), n->dbg_stop);
     if (two_streams && (rc = ensure_side_stream(n))) return rc;
     HeadBwd hd;
     hd.feat = feat; hd.h1 = h1; hd.out = o; hd.norms = norms; hd.dout = dout;
@@ -1597,22 +1603,15 @@ int ocl_net_backward(ocl_net* n, int slot, const float* dout, int accumulate, vo
     key.c = repack_mask;
     key.p = (uint64_t)(uintptr_t)P;
     rc = two_streams ? body() : run_replayed(n, key, s, body);   // (single-stream sequences only: see ocl_net_forward_segments)
-    if (repack) {
-        n->pack_src = P;
-        n->pack_have = repack_mask;
-        n->pack_stream = s;
-    }
+    if (repack) note_packed(n, P, repack_mask, s);
     n->bsums_clean = false;
     return rc;
 }
 
 int ocl_test_net_forms(int hw, int nf, int N, int groups, int train, ocl_test_net_form* out, int cap) {
     OCL_REQUIRE(N > 0 && groups > 0 && N % groups == 0 && (train || groups == 1), "test_net_forms: N=%d groups=%d train=%d", N, groups, train);
-    ocl_net_desc d;
-    memset(&d, 0, sizeof(d));
-    d.in_h = d.in_w = hw; d.nf = nf; d.n_classes = 10; d.head = 0; d.max_batch = N; d.n_slots = 1;
     ocl_net* n = nullptr;
-    int rc = ocl_net_create(&d, &n);
+    int rc = make_test_net(hw, nf, 10, 0, 0, N, &n);
     if (rc != OCL_OK) return rc;
     PlanSet ps;
     rc = make_plan_set(n, N, groups, &ps);
@@ -1671,11 +1670,8 @@ int ocl_test_head(ocl_test_head_args* a, void* stream) {
     OCL_REQUIRE(a->head == 0 || a->norms, "test_head: norms");
     OCL_REQUIRE((a->head != 1 && a->head != 2) || (a->h2 && a->dh2), "test_head: h2 / dh2");
     OCL_REQUIRE(a->head != 1 || (a->h1 && a->dh1), "test_head: h1 / dh1");
-    ocl_net_desc d;
-    memset(&d, 0, sizeof(d));
-    d.in_h = d.in_w = a->hw; d.nf = a->nf; d.n_classes = a->n_classes; d.head = a->head; d.feat_dim = a->feat_dim; d.max_batch = a->n; d.n_slots = 1;
     ocl_net* n = nullptr;
-    int rc = ocl_net_create(&d, &n);
+    int rc = make_test_net(a->hw, a->nf, a->n_classes, a->head, a->feat_dim, a->n, &n);
     if (rc != OCL_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int N = a->n;
@@ -1686,14 +1682,14 @@ int ocl_test_head(ocl_test_head_args* a, void* stream) {
     bool wrote = false;
     if (rc == OCL_OK)
         rc = head_forward(n, a->params, (float*)a->feat, a->h1, a->h2, a->norms, a->out, N, s, nullptr, &wrote);
-    const bool two_streams = backward_two_streams(n, N);
+    const bool two_streams = two_streams_at(in_pixels(n, N), n->dbg_stop);
     if (rc == OCL_OK && two_streams) rc = ensure_side_stream(n);
     if (rc == OCL_OK) {
         HeadBwd hd;
         hd.feat = a->feat; hd.h1 = a->h1; hd.out = a->out; hd.norms = a->norms; hd.dout = a->dout;
         hd.dfeat = a->dfeat; hd.dh1 = a->dh1; hd.dh2 = a->dh2;
         rc = head_backward(n, a->params, a->grads, hd, N, a->accumulate, s, two_streams);
-        a->side_stream = head_on_side_stream(n, N, two_streams) ? 1 : 0;
+        a->side_stream = head_side_at(in_pixels(n, N), two_streams) ? 1 : 0;
     }
     if (n->s2) (void)hipStreamSynchronize(n->s2);
     if (hipStreamSynchronize(s) != hipSuccess && rc == OCL_OK) {
@@ -1745,10 +1741,9 @@ int ocl_net_debug_copy(ocl_net* n, int slot, int what, int index, float* dst, in
         src = S + n->blocks[index].a1_off;
         cnt = (int64_t)N * c.Ho * c.Wo * c.Cout;
         if (n->slot_fused[slot]) {   // the pass never wrote a1: materialise it from the raw output and the saved statistics
-            const BnInfo& b1 = n->bns[c.bn];
+            const BnView v = bn_view(n, n->params, nullptr, S, c.bn);
             const int G = std::max(1, n->slot_groups[slot]);
-            int rc = launch_bn_apply_saved(S + c.y_off, S + b1.save_off, S + b1.save_off + (int64_t)kGmax * b1.C, n->params + n->tensors[b1.gamma_t].off,
-                                           n->params + n->tensors[b1.beta_t].off, S + n->blocks[index].a1_off, (int64_t)(N / G) * c.Ho * c.Wo, G, b1.C, s);
+            int rc = launch_bn_apply_saved(S + c.y_off, v.save_mean, v.save_invstd, v.gamma, v.beta, S + n->blocks[index].a1_off, (int64_t)(N / G) * c.Ho * c.Wo, G, v.C, s);
             if (rc != OCL_OK) return rc;
         }
     } else {
@@ -1766,11 +1761,8 @@ int ocl_net_debug_copy(ocl_net* n, int slot, int what, int index, float* dst, in
 namespace ocl {
 
 int net_test_tables(int hw, int nf, NetTestTables* out) {
-    ocl_net_desc d;
-    memset(&d, 0, sizeof(d));
-    d.in_h = d.in_w = hw; d.nf = nf; d.n_classes = 10; d.head = 0; d.max_batch = 1; d.n_slots = 1;
     ocl_net* n = nullptr;
-    int rc = ocl_net_create(&d, &n);
+    int rc = make_test_net(hw, nf, 10, 0, 0, 1, &n);
     if (rc != OCL_OK) return rc;
     make_descs(n, &out->pack, &out->fold);
     out->n_params = n->n_params;

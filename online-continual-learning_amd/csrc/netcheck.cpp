@@ -13,7 +13,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
-#include "../../include/ocl_hip.h"
+#include "common.h"   // (the switch reader only: header-only, nothing of the library's internals is linked)
 
 #define OK(x)                                                                           \
     do {                                                                                \
@@ -105,7 +105,7 @@ int main(int argc, char** argv) {
     OK(ocl_net_bind(net, p, g, r, nbt, ws, wsb));
     hipStream_t s;
     CK(hipStreamCreate(&s));
-    const int passes = getenv("NETCHECK_PASSES") ? atoi(getenv("NETCHECK_PASSES")) : 3;   // (the third pass runs replayed with OCL_GRAPH=1)
+    const int passes = ocl::env_int("NETCHECK_PASSES", 3);   // (the third pass runs replayed with OCL_GRAPH=1)
     for (int it = 0; it < passes; ++it) {
         OK(ocl_net_forward(net, x, n, groups, OCL_FWD_TRAIN | OCL_FWD_SAVE_TAPE | OCL_FWD_UPDATE_RUNNING, nullptr, feat, out, 0, s));
         OK(ocl_net_backward(net, 0, dout, 0, s));

@@ -652,8 +652,8 @@ int plan_wgrad(int N, int Hin, int Win, int Cin, int Ho, int Wo, int Cout, int k
     // machine alone: fewer pixel splits, i.e. fewer slabs to write and to reduce)
     constexpr int env_kp = 128;
     // (OCL_WGRAD_TARGET / OCL_WGRAD_ENOUGH: measurement overrides, profiles/r6_wgrad_mtw_ab.txt)
-    static const int ov_target = [] { const char* e = getenv("OCL_WGRAD_TARGET"); return e ? atoi(e) : 0; }();
-    static const int ov_enough = [] { const char* e = getenv("OCL_WGRAD_ENOUGH"); return e ? atoi(e) : 0; }();
+    static const int ov_target = env_int("OCL_WGRAD_TARGET", 0);
+    static const int ov_enough = env_int("OCL_WGRAD_ENOUGH", 0);
     const int env_target = wg_target > 0 ? wg_target : (ov_target > 0 ? ov_target : 512);
     const int env_enough = wg_target > 0 ? std::max(1, wg_target * 3 / 4) : (ov_enough > 0 ? ov_enough : 384);
     for (int pass = 0; pass < 2 && !found; ++pass) {
@@ -725,7 +725,7 @@ int plan_wgrad(int N, int Hin, int Win, int Cin, int Ho, int Wo, int Cout, int k
     // which tests/test_gpu_netcheck.py uses as the reference of its A/B).  Row groups (16 gradient rows) per wave: the smallest count
     // that covers the rows with one row block, i.e. the patch is staged once per pixel tile; the pixel split aims at 256 workgroups (the
     // block sums of the epilogue cost about one pixel tile's MFMAs, so fewer, longer workgroups than the 16x16x4 form).
-    static const int env_q = [] { const char* e = getenv("OCL_WGRAD_Q"); return e ? atoi(e) : 1; }();
+    static const int env_q = env_int("OCL_WGRAD_Q", 1);
     // (the stem's 9 units fill 3 of 4 waves: measured slower; the block sums of the epilogue cost about 1.7 pixel tiles, and the form
     // runs one workgroup per CU: it pays from ~6 tiles of 128 pixels per workgroup at 256 workgroups -- SCR's 220 views yes,
     // 20 images of 84 x 84 no (+40 us); OCL_WGRAD_Q=2 lifts that limit for the planner test)

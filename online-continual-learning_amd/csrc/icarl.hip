@@ -13,7 +13,7 @@
 //
 // The shape of the CE family (small_ops.hip) and of distill.hip: a single workgroup of four waves, one wave per row, reductions by wave
 // shuffles, the per-wave partial sums through LDS and added in index order -- no atomics, a fixed order of summation, two runs give the
-// same bits.  The loss is element-wise, so a row is read exactly once either way; a row of up to BCE_REG * 64 columns has all its loads
+// same bits.  The loss is element-wise, so a row is read exactly once either way; a row of up to ROW_REG * 64 columns has all its loads
 // issued before the arithmetic and sits in registers (lane l holds columns l, l + 64, ...), a longer row takes a strided loop.
 //
 // Columns the reference slices away are never READ: logits and teacher columns j >= n_cls, teacher columns j >= n_old (a NaN there
@@ -24,12 +24,11 @@
 // built with fast-math.
 #include <cmath>
 
-#include "common.h"
+#include "row_dev.h"
 
 using namespace ocl;
 
-static constexpr int BCE_REG = 4;   // registers per lane and per operand: rows of up to 256 columns stay in registers
-
+// (Its own iterator, row loop and fold, not row_dev.h's: see "not shared" there.  ROW_REG, row_in_regs and row_check_output are shared.)
 // sig(x) = 1 / (1 + exp(-x)) without overflow, from e = exp(-|x|) (which the loss's log1p term needs as well)
 __device__ __forceinline__ float exp_neg_abs(float x) { return expf(-fabsf(x)); }
 __device__ __forceinline__ float sigmoid(float x) {
@@ -43,10 +42,10 @@ __device__ __forceinline__ float sigmoid(float x) {
 template <bool REG, bool KD>
 __device__ __forceinline__ void bce_row(const float* __restrict__ s, const float* __restrict__ t, int c, int n_cls, int n_old, int64_t p,
                                         int lane, float n_f, float* __restrict__ dx, double& acc_old, double& acc_new) {
-    float sv[BCE_REG], tv[BCE_REG];
+    float sv[ROW_REG], tv[ROW_REG];
     if (REG) {
 #pragma unroll
-        for (int k = 0; k < BCE_REG; ++k) {
+        for (int k = 0; k < ROW_REG; ++k) {
             const int j = lane + 64 * k;
             sv[k] = j < n_cls ? s[j] : 0.f;
             tv[k] = (KD && j < n_old) ? t[j] : 0.f;
@@ -68,7 +67,7 @@ __device__ __forceinline__ void bce_row(const float* __restrict__ s, const float
     };
     if (REG) {
 #pragma unroll
-        for (int k = 0; k < BCE_REG; ++k) {
+        for (int k = 0; k < ROW_REG; ++k) {
             const int j = lane + 64 * k;
             if (j < n_cls) f(j, sv[k], tv[k]);
         }
@@ -117,14 +116,12 @@ int ocl_bce_distill_fwd_bwd(const float* logits, const float* teacher, const int
     OCL_REQUIRE(n_old >= 0 && n_old <= n_cls && n_cls <= c, "bce_distill: n_old=%d n_cls=%d c=%d (0 <= n_old <= n_cls <= c)", n_old, n_cls, c);
     OCL_REQUIRE(teacher || n_old == 0, "bce_distill: n_old=%d without a teacher (a null teacher requires n_old == 0)", n_old);
     const size_t bytes = (size_t)n * (size_t)c * sizeof(float);
-    if (dlogits) {
-        OCL_REQUIRE(!ranges_overlap(dlogits, bytes, logits, bytes), "bce_distill: dlogits overlaps logits");
-        OCL_REQUIRE(!(teacher && ranges_overlap(dlogits, bytes, teacher, bytes)), "bce_distill: dlogits overlaps teacher");
-        OCL_REQUIRE(!ranges_overlap(dlogits, bytes, pos, (size_t)n_stream * sizeof(int64_t)), "bce_distill: dlogits overlaps pos");
-    }
+    if (int rc = row_check_output("bce_distill", {dlogits, bytes, "dlogits"},
+                                  {{logits, bytes, "logits"}, {teacher, bytes, "teacher"}, {pos, (size_t)n_stream * sizeof(int64_t), "pos"}}))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     ProfScope ps(PROF_HEAD, s);
-    const bool reg = c <= BCE_REG * 64, kd = n_old > 0;
+    const bool reg = row_in_regs(c), kd = n_old > 0;
     auto k = kd ? (reg ? bce_distill_kernel<true, true> : bce_distill_kernel<false, true>)
                 : (reg ? bce_distill_kernel<true, false> : bce_distill_kernel<false, false>);
     hipLaunchKernelGGL(k, dim3(1), dim3(256), 0, s, logits, teacher, pos, n, n_stream, c, n_cls, n_old, loss_out, dlogits);

@@ -2,6 +2,7 @@
 // small MFMA GEMM.  HBM/latency-bound integer+fp32 work: coalesced 16-B accesses, LDS sorts, one
 // workgroup per row — none of this is reshaped into GEMMs.
 #include "flat_dev.h"
+#include "row_dev.h"
 #include <limits.h>
 #include <math.h>
 #include <vector>
@@ -269,54 +270,31 @@ __global__ void __launch_bounds__(64) cosine_finish_kernel(const double* __restr
 }
 
 // =====================================================================================================
-// K6 cross-entropy: single workgroup, one wave per row, deterministic mean
+// K6 cross-entropy: single workgroup, one wave per row, deterministic mean (row_dev.h has the loop, the fold and the row formulas)
 // =====================================================================================================
-// exact (optional): the row loss with its three pieces (log of the sum, the max, the label's logit) combined in double, for a caller
-// that subtracts two row losses (mir_kernel: the difference is small against the losses, whose fp32 roundings would dominate it)
-__device__ __forceinline__ float ce_row(const float* __restrict__ x, int c, int64_t y, int lane, float* __restrict__ dx,
-                                        float scale, double* exact = nullptr) {
-    float m = -INFINITY;
-    for (int j = lane; j < c; j += 64) m = fmaxf(m, x[j]);
-    m = wave_max(m);
-    float s = 0.f;
-    for (int j = lane; j < c; j += 64) s += expf(x[j] - m);
-    s = wave_sum(s);
-    const float lse = logf(s) + m;
-    const float xy = (uint64_t)y < (uint64_t)c ? x[y] : NAN;   // a label outside the row is no address: the row's loss is NaN (K6, K12)
-    if (dx) {
-        const float inv = 1.0f / s;
-        for (int j = lane; j < c; j += 64) {
-            float p = expf(x[j] - m) * inv;
-            dx[j] = (p - ((int64_t)j == y ? 1.f : 0.f)) * scale;
-        }
-    }
-    if (exact) *exact = ((double)logf(s) + (double)m) - (double)xy;
-    return lse - xy;
-}
-
 __global__ void __launch_bounds__(256) ce_kernel(const float* __restrict__ logits, const int64_t* __restrict__ y, int n, int c,
                                                  int reduction, float* __restrict__ loss_out, float* __restrict__ dlogits) {
-    __shared__ float part[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const float scale = reduction == 1 ? 1.0f / (float)n : 1.0f;
-    float acc = 0.f;
-    for (int r = wid; r < n; r += 4) {
-        float l = ce_row(logits + (int64_t)r * c, c, y[r], lane, dlogits ? dlogits + (int64_t)r * c : nullptr, scale);
+    float acc[1] = {0.f};
+    ROW_FOR_EACH(r, n) {
+        float l = ce_row(RowCols<false>(logits + (int64_t)r * c, nullptr, lane, c, 0, 0.f), c, y[r],
+                         dlogits ? dlogits + (int64_t)r * c : nullptr, scale);
         if (reduction == 0) {
             if (lane == 0) loss_out[r] = l;
         } else {
-            acc += l;
+            acc[0] += l;
         }
     }
     if (reduction == 1) {
-        if (lane == 0) part[wid] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) loss_out[0] = (part[0] + part[1] + part[2] + part[3]) / (float)n;
+        row_fold(acc);
+        if (threadIdx.x == 0) loss_out[0] = acc[0] / (float)n;
     }
 }
 
 // Cross-entropy over a column segment (agents/base.py:96-108, the labels trick and the separated softmax): seg[j] in {-1, 0, 1, ...}
 // assigns every logit column to a segment (-1: takes no part); row r is a softmax over the columns of its label's segment.
+// (Its own row and loop, not row_dev.h's: see "not shared" there.)
 __device__ __forceinline__ float ce_row_seg(const float* __restrict__ x, const int* __restrict__ seg, int c, int64_t y, int lane,
                                             float* __restrict__ dx, float scale) {
     // a label outside the row is no address (K6): its segment id is one no column has (ids are >= -1), so the row's softmax is empty
@@ -361,51 +339,35 @@ __global__ void __launch_bounds__(256) ce_seg_kernel(const float* __restrict__ l
 // gradient w.r.t. the student scores, (softmax(s/T) - softmax(t/T)) * T / n.  One wave per row.
 __global__ void __launch_bounds__(256) kd_kernel(const float* __restrict__ scores, const float* __restrict__ target, int n, int c,
                                                  float T, float* __restrict__ loss_out, float* __restrict__ dscores) {
-    __shared__ float part[4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    // scores / T as the reference divides (kd_manager.py:7-8): a multiplication by the rounded 1 / T is off by up to |x| / T * 2^-24 in the
-    // logit for a T that is no power of two -- 2e-5 at |x| = 2000, T = 3, which the softmax turns into a relative error of that size
-    float acc = 0.f;
-    for (int r = wid; r < n; r += 4) {
-        const float* s = scores + (int64_t)r * c;
-        const float* t = target + (int64_t)r * c;
-        float ms = -INFINITY, mt = -INFINITY;
-        for (int j = lane; j < c; j += 64) {
-            ms = fmaxf(ms, s[j] / T);
-            mt = fmaxf(mt, t[j] / T);
-        }
-        ms = wave_max(ms);
-        mt = wave_max(mt);
-        float ss = 0.f, st = 0.f;
-        for (int j = lane; j < c; j += 64) {
-            ss += expf(s[j] / T - ms);
-            st += expf(t[j] / T - mt);
-        }
-        ss = wave_sum(ss);
-        st = wave_sum(st);
-        const float lse = logf(ss) + ms, inv_s = 1.0f / ss, inv_t = 1.0f / st;
-        float row = 0.f;
-        for (int j = lane; j < c; j += 64) {
-            const float pt = expf(t[j] / T - mt) * inv_t;
-            row -= pt * (s[j] / T - lse);
-            if (dscores) dscores[(int64_t)r * c + j] = (expf(s[j] / T - ms) * inv_s - pt) * T / (float)n;
-        }
-        acc += wave_sum(row);
+    const int lane = threadIdx.x & 63;
+    float acc[1] = {0.f};
+    ROW_FOR_EACH(r, n) {
+        const RowCols<false> cols(scores + (int64_t)r * c, target + (int64_t)r * c, lane, c, c, 0.f);
+        KdRow kd(T);
+        cols.each([&](int, float s, float t) { kd.max_of(s, t); });
+        kd.max_done();
+        cols.each([&](int, float s, float t) { kd.sum_of(s, t); });
+        kd.sum_done();
+        cols.each([&](int j, float s, float t) {
+            const float pt = kd.pt_of(t);
+            kd.term(s, pt);
+            if (dscores) dscores[(int64_t)r * c + j] = kd.grad(kd.ps_of(s), pt, (float)n);
+        });
+        acc[0] += wave_sum(kd.row);
     }
-    if (lane == 0) part[wid] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) loss_out[0] = (part[0] + part[1] + part[2] + part[3]) / (float)n * T * T;
+    row_fold(acc);
+    if (threadIdx.x == 0) loss_out[0] = acc[0] / (float)n * T * T;
 }
 
-// K12 MIR: post CE - pre CE per sample
+// K12 MIR: post CE - pre CE per sample; four rows per workgroup, no sum across the rows
 __global__ void __launch_bounds__(256) mir_kernel(const float* __restrict__ pre, const float* __restrict__ post,
                                                   const int64_t* __restrict__ y, int n, int c, float* __restrict__ out) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int r = blockIdx.x * 4 + wid;
+    const int r = blockIdx.x * ROW_WAVES + wid;
     if (r >= n) return;
     double a, b;
-    ce_row(pre + (int64_t)r * c, c, y[r], lane, nullptr, 1.f, &a);
-    ce_row(post + (int64_t)r * c, c, y[r], lane, nullptr, 1.f, &b);
+    ce_row(RowCols<false>(pre + (int64_t)r * c, nullptr, lane, c, 0, 0.f), c, y[r], nullptr, 1.f, &a);
+    ce_row(RowCols<false>(post + (int64_t)r * c, nullptr, lane, c, 0, 0.f), c, y[r], nullptr, 1.f, &b);
     if (lane == 0) out[r] = (float)(b - a);
 }
 

@@ -294,6 +294,14 @@ def ewc_fisher_normalize(running, fisher_hat_out, workspace=None, minmax_out=Non
 
 
 # ---- K6 ----------------------------------------------------------------------------------------------
+def _refuse(op, what, t, dtype, shape):
+    """The K6b-K6d functions convert nothing: anything but a contiguous tensor of this dtype and shape is refused."""
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise RuntimeError("%s: %s must be a contiguous %s tensor of shape %s, got %s %s%s" % (
+            op, what, dtype, tuple(shape), getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ())),
+            "" if not torch.is_tensor(t) or t.is_contiguous() else " (not contiguous)"))
+
+
 def cross_entropy(logits, y, reduction="mean", want_grad=True, dl_out=None):
     """(loss, dlogits): torch.nn.CrossEntropyLoss / F.cross_entropy(reduction='none').  dl_out: a contiguous float32 [n, c] tensor
     (e.g. a row block of a larger gradient buffer) that receives dlogits instead of a fresh one."""
@@ -348,21 +356,15 @@ def ce_kd_blend(logits, y, teacher_logits, T, w_new, w_old, want_grad=True, dl_o
     loss3[0].  teacher_logits None (no teacher yet): kd = 0, the gradient is the cross-entropy's.  Nothing is made contiguous or
     converted here: a tensor of another dtype, shape, layout or device is refused.  dl_out: a contiguous float32 [n, c] tensor (e.g. a
     row block of a larger gradient buffer) that receives dlogits instead of a fresh one."""
-    def refuse(what, t, dtype, shape):
-        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-            raise RuntimeError("ce_kd_blend: %s must be a contiguous %s tensor of shape %s, got %s %s%s" % (
-                what, dtype, tuple(shape), getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ())),
-                "" if not torch.is_tensor(t) or t.is_contiguous() else " (not contiguous)"))
-
     if not torch.is_tensor(logits) or logits.dim() != 2:
         raise RuntimeError("ce_kd_blend: logits must be a [n, c] tensor")
-    refuse("logits", logits, torch.float32, logits.shape)
+    _refuse("ce_kd_blend", "logits", logits, torch.float32, logits.shape)
     n, c = logits.shape
-    refuse("y", y, torch.int64, (n,))
+    _refuse("ce_kd_blend", "y", y, torch.int64, (n,))
     if teacher_logits is not None:
-        refuse("teacher_logits", teacher_logits, torch.float32, (n, c))
+        _refuse("ce_kd_blend", "teacher_logits", teacher_logits, torch.float32, (n, c))
     if dl_out is not None:
-        refuse("dl_out", dl_out, torch.float32, (n, c))
+        _refuse("ce_kd_blend", "dl_out", dl_out, torch.float32, (n, c))
     for what, t in (("logits", logits), ("y", y), ("teacher_logits", teacher_logits), ("dl_out", dl_out)):
         if t is not None and (not t.is_cuda or t.device != logits.device):
             raise RuntimeError("ce_kd_blend: %s is on %s; every tensor lives on the logits' GPU" % (what, t.device))
@@ -383,27 +385,21 @@ def bce_distill(logits, teacher_logits, pos, n_stream, n_cls, n_old, want_grad=T
     n_cls on.  pos: int64 [n_stream], the target column of each stream row.  teacher_logits None (no teacher yet) requires n_old == 0.
     Nothing is made contiguous or converted here: a tensor of another dtype, shape, layout or device is refused.  dl_out: a contiguous
     float32 [n, c] tensor (e.g. a row block of a larger gradient buffer) that receives dlogits instead of a fresh one."""
-    def refuse(what, t, dtype, shape):
-        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-            raise RuntimeError("bce_distill: %s must be a contiguous %s tensor of shape %s, got %s %s%s" % (
-                what, dtype, tuple(shape), getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ())),
-                "" if not torch.is_tensor(t) or t.is_contiguous() else " (not contiguous)"))
-
     if not torch.is_tensor(logits) or logits.dim() != 2:
         raise RuntimeError("bce_distill: logits must be a [n, c] tensor")
-    refuse("logits", logits, torch.float32, logits.shape)
+    _refuse("bce_distill", "logits", logits, torch.float32, logits.shape)
     n, c = logits.shape
     n_stream, n_cls, n_old = int(n_stream), int(n_cls), int(n_old)
     if not (1 <= n_stream <= n and 0 <= n_old <= n_cls <= c):
         raise RuntimeError("bce_distill: n_stream=%d n_cls=%d n_old=%d with logits %s (1 <= n_stream <= n, 0 <= n_old <= n_cls <= c)"
                            % (n_stream, n_cls, n_old, (n, c)))
-    refuse("pos", pos, torch.int64, (n_stream,))
+    _refuse("bce_distill", "pos", pos, torch.int64, (n_stream,))
     if teacher_logits is not None:
-        refuse("teacher_logits", teacher_logits, torch.float32, (n, c))
+        _refuse("bce_distill", "teacher_logits", teacher_logits, torch.float32, (n, c))
     elif n_old:
         raise RuntimeError("bce_distill: n_old=%d without teacher_logits" % n_old)
     if dl_out is not None:
-        refuse("dl_out", dl_out, torch.float32, (n, c))
+        _refuse("bce_distill", "dl_out", dl_out, torch.float32, (n, c))
     for what, t in (("logits", logits), ("pos", pos), ("teacher_logits", teacher_logits), ("dl_out", dl_out)):
         if t is not None and (not t.is_cuda or t.device != logits.device):
             raise RuntimeError("bce_distill: %s is on %s; every tensor lives on the logits' GPU" % (what, t.device))
@@ -423,15 +419,9 @@ def row_argmax_groupsum(x, col_group=None, sel=0, want_argmax=True, want_sum=Tru
     an empty group gives +0.0).  Nothing is made contiguous or converted here: a tensor of another dtype, shape, layout or device is
     refused.  argmax_out / sum_out: contiguous int64 / float64 [n] tensors (e.g. a row block of a loader-long table) that receive the
     results instead of fresh ones; giving one asks for that result."""
-    def refuse(what, t, dtype, shape):
-        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-            raise RuntimeError("row_argmax_groupsum: %s must be a contiguous %s tensor of shape %s, got %s %s%s" % (
-                what, dtype, tuple(shape), getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ())),
-                "" if not torch.is_tensor(t) or t.is_contiguous() else " (not contiguous)"))
-
     if not torch.is_tensor(x) or x.dim() != 2:
         raise RuntimeError("row_argmax_groupsum: x must be a [n, c] tensor")
-    refuse("x", x, torch.float32, x.shape)
+    _refuse("row_argmax_groupsum", "x", x, torch.float32, x.shape)
     n, c = x.shape
     if n < 1 or c < 1:
         raise RuntimeError("row_argmax_groupsum: x is %s (n and c must be >= 1)" % ((n, c),))
@@ -439,11 +429,11 @@ def row_argmax_groupsum(x, col_group=None, sel=0, want_argmax=True, want_sum=Tru
     if not (want_argmax or want_sum):
         raise RuntimeError("row_argmax_groupsum: neither the arg-max nor the sums are asked for")
     if col_group is not None:
-        refuse("col_group", col_group, torch.int32, (c,))
+        _refuse("row_argmax_groupsum", "col_group", col_group, torch.int32, (c,))
     if argmax_out is not None:
-        refuse("argmax_out", argmax_out, torch.int64, (n,))
+        _refuse("row_argmax_groupsum", "argmax_out", argmax_out, torch.int64, (n,))
     if sum_out is not None:
-        refuse("sum_out", sum_out, torch.float64, (n,))
+        _refuse("row_argmax_groupsum", "sum_out", sum_out, torch.float64, (n,))
     for what, t in (("x", x), ("col_group", col_group), ("argmax_out", argmax_out), ("sum_out", sum_out)):
         if t is not None and (not t.is_cuda or t.device != x.device):
             raise RuntimeError("row_argmax_groupsum: %s is on %s; every tensor lives on x's GPU" % (what, t.device))

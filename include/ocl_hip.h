@@ -221,6 +221,32 @@ int ocl_ce_kd_blend_fwd_bwd(const float* logits, const int64_t* y, const float* 
 int ocl_bce_distill_fwd_bwd(const float* logits, const float* teacher, const int64_t* pos, int n, int n_stream, int c, int n_cls,
                             int n_old, float* loss_out, float* dlogits, void* stream);
 
+/* ---- K6e: Dark Experience Replay's loss (DER / DER++) ---------------------------------------------------
+ * Buzzega et al., NeurIPS 2020, loss and gradient in ONE launch.  logits is one contiguous block of
+ * n0 + n1 + n2 rows of c columns: the stream batch, the logit-replay batch, the label-replay batch.
+ *   ce    = mean_{r < n0}(lse(s_r) - s_r[y0_r])
+ *   mse   = sum_{r in block 1, j} (s_rj - z_rj)^2 / (n1 * c)        z_r = stored[slots[r]]
+ *   ce_m  = mean_{r in block 2}(lse(s_r) - s_r[y2_r])
+ *   loss_out[4] = {ce + alpha * mse + beta * ce_m, ce, mse, ce_m}
+ *   dlogits: block 0 (softmax - onehot) / n0;  block 1 alpha * 2 * (s - z) / (n1 * c);
+ *            block 2 beta * (softmax - onehot) / n2
+ * y0 is int64 [n0], y2 int64 [n2], stored float [m, c] (the memory's logit table), slots int64 [n1] or NULL
+ * (rows 0 .. n1 - 1 of stored).  n1 == 0 or n2 == 0 is allowed: the term is 0, nothing of it is read, and
+ * stored, slots and y2 may then be NULL.  With n1 == n2 == 0 the loss and dlogits are the bits of
+ * ocl_ce_fwd_bwd(reduction = mean).  s - z is formed once for the loss and the gradient: a stored row that
+ * equals today's row bit for bit gives exactly 0 for both.  A label outside [0, c) is no address: that row's
+ * loss is NaN and no one-hot is subtracted.  A slot outside [0, m) is no address: that row's z is NaN and
+ * nothing is read.  Block 1 never reads a label.  dlogits may be NULL (losses only: the same four values).
+ * One workgroup, one wave per row; the squared error's element, row and cross-row sums and block 2's row
+ * losses and their sum in double (block 0's in float: they are ocl_ce_fwd_bwd's); every sum in a fixed order
+ * without atomics: two runs give the same bits.  A row of up to 256 columns is held in
+ * registers; a longer one takes strided loops.  Ordered on `stream`, no host synchronisation.  OCL_ERR_ARG
+ * ("der_loss: ...") before any launch, nothing written, for a null logits, y0 or loss_out, n0 < 1, n1 < 0,
+ * n2 < 0, c < 1, n1 > 0 with a null stored or m < 1, n2 > 0 with a null y2, a non-finite alpha or beta, or a
+ * dlogits that overlaps logits or stored. */
+int ocl_der_fwd_bwd(const float* logits, const int64_t* y0, const int64_t* y2, const float* stored, const int64_t* slots, int n0,
+                    int n1, int n2, int c, int m, float alpha, float beta, float* loss_out, float* dlogits, void* stream);
+
 /* ---- K6d: per-row arg-max and group sum (evaluate()'s error analysis) -----------------------------------
  * agents/base.py:179-203 and :217-218.  x is [n, c], row-major and contiguous.  Per row r, in ONE launch:
  *   argmax_out[r] = the smallest column index among the row's maxima; a NaN compares as larger than everything

@@ -1,6 +1,6 @@
 // The one row skeleton of the per-row loss kernels (K6 cross-entropy, segmented cross-entropy and distillation, K12 MIR in small_ops.hip;
-// K6b ce_kd_blend in distill.hip; K6c bce_distill in icarl.hip; K6d row_argmax_groupsum in rowstats.hip): one wave per row, lane l owning
-// columns l, l + 64, ..., and the two row formulas that more than one of them evaluates.
+// K6b ce_kd_blend in distill.hip; K6c bce_distill in icarl.hip; K6d row_argmax_groupsum in rowstats.hip; K6e der_loss in der.hip): one
+// wave per row, lane l owning columns l, l + 64, ..., and the two row formulas that more than one of them evaluates.
 //
 // What is fixed here, and why the code has this shape:
 //   * RowCols: the lane's columns of a row and of a second operand beside it (a teacher's row, the columns' segment or group ids),

@@ -119,6 +119,7 @@ SIGNATURES = {
     "ocl_kd_fwd_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]),
     "ocl_ce_kd_blend_fwd_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, f32, f32, f32, vp, vp, vp]),
     "ocl_bce_distill_fwd_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "ocl_der_fwd_bwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, f32, vp, vp, vp]),
     "ocl_row_argmax_groupsum": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]),
     "ocl_supcon_workspace_bytes": (i64, [C.c_int]),
     "ocl_supcon_fwd_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f32, vp, vp, vp, vp]),

@@ -63,10 +63,17 @@ exemplar_agents = _Lazy({
 })
 
 
+# agents that replay stored logits beside the labels (Dark Experience Replay; an addition beyond the reference's registry; section 1b
+# as well, and a table of its own for the same reason)
+logit_replay_agents = _Lazy({
+    'DER': ('.agents.der', 'Der'),
+})
+
+
 def get_agent(key):
     """The agent class registered under `key`: `agents` first, then `extra_agents`, `regularization_agents`, `distillation_agents`,
-    `offline_agents` and `exemplar_agents`; KeyError otherwise."""
-    for table in (agents, extra_agents, regularization_agents, distillation_agents, offline_agents, exemplar_agents):
+    `offline_agents`, `exemplar_agents` and `logit_replay_agents`; KeyError otherwise."""
+    for table in (agents, extra_agents, regularization_agents, distillation_agents, offline_agents, exemplar_agents, logit_replay_agents):
         if key in table:
             return table[key]
     raise KeyError(key)

@@ -411,6 +411,51 @@ def bce_distill(logits, teacher_logits, pos, n_stream, n_cls, n_old, want_grad=T
     return loss, dl
 
 
+# ---- K6e ---------------------------------------------------------------------------------------------
+def der_loss(logits, y0, y2, stored, slots, n0, n1, n2, alpha, beta, want_grad=True, dl_out=None):
+    """(loss4, dlogits) of Dark Experience Replay's loss (DER / DER++) in one launch.  `logits` [n0 + n1 + n2, c] is one block: the stream
+    batch, the logit-replay batch, the label-replay batch.  loss4 = [ce + alpha * mse + beta * ce_m, ce, mse, ce_m] with ce the mean
+    cross-entropy of the first n0 rows against `y0`, mse the mean squared error between the next n1 rows and stored[slots] (the logits
+    those images had when they entered the memory; slots None: rows 0 .. n1 - 1 of `stored`), ce_m the mean cross-entropy of the last n2
+    rows against `y2`; dlogits is the gradient of loss4[0].  n1 == 0 or n2 == 0 leaves the term out (0): `stored`, `slots`, `y2` may then
+    be None.  stored: float32 [m, c], read in place; slots: int64 [n1].  Nothing is made contiguous or converted here: a tensor of another
+    dtype, shape, layout or device is refused.  dl_out: a contiguous float32 [n0 + n1 + n2, c] tensor (e.g. a row block of a larger
+    gradient buffer) that receives dlogits instead of a fresh one."""
+    if not torch.is_tensor(logits) or logits.dim() != 2:
+        raise RuntimeError("der_loss: logits must be a [n0 + n1 + n2, c] tensor")
+    _refuse("der_loss", "logits", logits, torch.float32, logits.shape)
+    n, c = logits.shape
+    n0, n1, n2 = int(n0), int(n1), int(n2)
+    if not (n0 >= 1 and n1 >= 0 and n2 >= 0 and n0 + n1 + n2 == n and c >= 1):
+        raise RuntimeError("der_loss: n0=%d n1=%d n2=%d with logits %s (n0 >= 1, n1 >= 0, n2 >= 0, n0 + n1 + n2 rows, c >= 1)"
+                           % (n0, n1, n2, (n, c)))
+    _refuse("der_loss", "y0", y0, torch.int64, (n0,))
+    if n2 or y2 is not None:
+        _refuse("der_loss", "y2", y2, torch.int64, (n2,))
+    m = 0
+    if n1 or stored is not None:
+        if not torch.is_tensor(stored) or stored.dim() != 2 or stored.shape[0] < 1:
+            raise RuntimeError("der_loss: stored must be a [m, c] tensor with m >= 1")
+        m = stored.shape[0]
+        _refuse("der_loss", "stored", stored, torch.float32, (m, c))
+    if slots is not None:
+        _refuse("der_loss", "slots", slots, torch.int64, (n1,))
+    elif n1 > m:
+        raise RuntimeError("der_loss: n1=%d rows without slots, but stored has %d rows" % (n1, m))
+    if dl_out is not None:
+        _refuse("der_loss", "dl_out", dl_out, torch.float32, (n, c))
+    for what, t in (("logits", logits), ("y0", y0), ("y2", y2), ("stored", stored), ("slots", slots), ("dl_out", dl_out)):
+        if t is not None and (not t.is_cuda or t.device != logits.device):
+            raise RuntimeError("der_loss: %s is on %s; every tensor lives on the logits' GPU" % (what, t.device))
+    ffi.init()
+    loss = torch.empty(4, dtype=torch.float32, device=logits.device)
+    dl = dl_out if dl_out is not None else (torch.empty_like(logits) if want_grad else None)
+    ffi.check(ffi.lib().ocl_der_fwd_bwd(ffi.ptr(logits), ffi.ptr(y0), ffi.ptr(y2) if n2 else None, ffi.ptr(stored) if n1 else None,
+                                        ffi.ptr(slots) if n1 else None, n0, n1, n2, c, m, float(alpha), float(beta), ffi.ptr(loss), ffi.ptr(dl),
+                                        ffi.stream()), "der_loss")
+    return loss, dl
+
+
 # ---- K6d ---------------------------------------------------------------------------------------------
 def row_argmax_groupsum(x, col_group=None, sel=0, want_argmax=True, want_sum=True, argmax_out=None, sum_out=None):
     """(argmax int64 [n] | None, sums float64 [n] | None) of the rows of x [n, c] in one launch: the smallest column index among each row's

@@ -5,7 +5,11 @@ Observable behaviour kept: while slots are free the stream fills them in order; 
 j ~ U[0, n_seen_so_far) with ONE `FloatTensor(k).uniform_(0, n_seen).long()` call on the torch CPU generator (what the CPU
 reference draws), is kept iff j < mem_size, and of several items drawing the same slot the last one wins while the slot keeps its
 first position in the returned list (the reference's dict).  Counters, the returned slot list and the host label mirror are
-maintained on the host; the overwrite itself is one gather + one scatter kernel per tensor."""
+maintained on the host; the overwrite itself is one gather + one scatter kernel per tensor.
+
+`extra` (optional keyword of update): a sequence of (table, rows) pairs -- further per-slot fields of the memory, such as the logits
+DER stores -- `table` a [mem_size, ...] tensor and `rows` one row per item of x.  Each table receives its rows at exactly the slots
+the images go to, on the fill path and on the overwrite path; nothing else changes (no draw, no counter, no returned slot)."""
 import numpy as np
 import torch
 
@@ -19,12 +23,14 @@ class Reservoir_update:
         pass
 
     @staticmethod
-    def _fill(buffer, x, y, y_host, count):
+    def _fill(buffer, x, y, y_host, count, extra=()):
         """Append the first `count` items at current_index."""
         lo = buffer.current_index
         hi = lo + count
         buffer.buffer_img[lo:hi].copy_(x[:count])
         buffer.buffer_label[lo:hi].copy_(y[:count])
+        for table, rows in extra:
+            table[lo:hi].copy_(rows[:count])
         buffer.label_host[lo:hi] = y_host[:count]
         buffer.current_index = hi
         buffer.n_seen_so_far += count
@@ -34,11 +40,16 @@ class Reservoir_update:
         capacity = buffer.buffer_img.size(0)
         y_host = _host_labels(y, kwargs.get("y_host"))
         n_items = x.size(0)
+        extra = tuple(kwargs.get("extra") or ())
+        for table, rows in extra:
+            if table.size(0) != capacity or rows.size(0) != n_items:
+                raise ValueError("Reservoir_update: an extra field needs one table row per slot and one row per item, got %d for %d slots "
+                                 "and %d for %d items" % (table.size(0), capacity, rows.size(0), n_items))
 
         free = max(0, capacity - buffer.current_index)
         if free:
             taken = min(free, n_items)
-            slots = self._fill(buffer, x, y, y_host, taken)
+            slots = self._fill(buffer, x, y, y_host, taken, extra)
             if taken == n_items:
                 # the reference refreshes the tracker only when the whole batch fitted (:22-27; its TODO at :30 notes the gap)
                 if getattr(buffer.params, "buffer_tracker", False):
@@ -47,6 +58,7 @@ class Reservoir_update:
                 return slots
         # the part of the batch that did not fit (all of it once the memory is full)
         x, y, y_host = x[free:], y[free:], y_host[free:]
+        extra = tuple((table, rows[free:]) for table, rows in extra)
 
         draws = torch.FloatTensor(x.size(0)).uniform_(0, buffer.n_seen_so_far).long()
         buffer.n_seen_so_far += x.size(0)
@@ -68,6 +80,8 @@ class Reservoir_update:
         items_dev = ops.upload(torch.tensor(items, dtype=torch.long), dev)
         ops.scatter_rows(buffer.buffer_img, slots_dev, ops.gather_rows(x.contiguous(), items_dev))
         ops.scatter_rows(buffer.buffer_label, slots_dev, ops.gather_rows(y.contiguous(), items_dev))
+        for table, rows in extra:
+            ops.scatter_rows(table, slots_dev, ops.gather_rows(rows.contiguous(), items_dev))
         buffer.label_host[np.asarray(slots, dtype=np.int64)] = y_host[np.asarray(items, dtype=np.int64)]
         debug.emit("reservoir", slots=list(slots))
         return slots

@@ -626,9 +626,9 @@ int ocl_test_head(ocl_test_head_args* a, void* stream);
 int ocl_test_head_side_min_batch(int hw);
 
 /* ---- which path a small-op entry point takes (tests) ------------------------------------------------
- * Host-only (no launch, no GPU): the kernel variant, grid and LDS size that the entry points of csrc/small_ops.hip choose for the
+ * Host-only (no launch, no GPU): the kernel variant, grid and LDS size that the small-op entry points (one file of csrc/ per kernel family) choose for the
  * given sizes and pointer VALUES (only their alignment is looked at; nothing is dereferenced).  The entry points call the same
- * functions to launch, so the answer cannot drift from what runs.  tests/test_cpu_small_ops.py requires a parity case in
+ * functions (csrc/small_ops.h) to launch, so the answer cannot drift from what runs.  tests/test_cpu_small_ops.py requires a parity case in
  * tests/small_op_cases.py for every OCL_PATH_* below.  args (int64 each), by op:
  *   ROWS        src, dst, row_bytes, n                  (ocl_gather_rows / ocl_scatter_rows)
  *   PAIR        src_a, dst_a, row_bytes_a, row_bytes_b, n

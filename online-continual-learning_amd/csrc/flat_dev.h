@@ -1,4 +1,4 @@
-// The one streaming skeleton of the flat-array kernels (K8 SGD, K8b Adam, K8c A-GEM, K8d EWC++, K8e clip): every kernel over the flat
+// The one streaming skeleton of the flat-array kernels (K8 SGD and K8b Adam in optim.hip, K8c A-GEM, K8d EWC++, K8e clip): every kernel over the flat
 // parameter or gradient array is this loop, these two reduction stages and this argument check, plus its own per-element mathematics.
 //
 // What is fixed here, and why the code has this shape:
@@ -14,7 +14,7 @@
 //     nothing is added") simply does not call load / store for it.
 //   * nothing that includes this header may be built with fast-math.
 // What is not shared: the min / max reduction of the Fisher normalisation (one user: ewc.hip keeps it), ewc_penalty_kernel's serial
-// fold, the cosine kernels' (r0 + r1) + (r2 + r3) block stage (small_ops.hip), and every grid formula but the reduction grid's.
+// fold, the cosine kernels' (r0 + r1) + (r2 + r3) block stage (cosine.hip), and every grid formula but the reduction grid's.
 #pragma once
 #include "common.h"
 #include <algorithm>

@@ -11,7 +11,7 @@
 // the one-hot scatter, zeros_like, the two cats, the sigmoid, the `for k in old_labels: target[:, k] = q[:, k]` loop of one strided
 // copy per old class, the loss, its row sum and mean, and autograd's walk back through them.
 //
-// The shape of the CE family (small_ops.hip) and of distill.hip: a single workgroup of four waves, one wave per row, reductions by wave
+// The shape of the CE family (row_losses.hip) and of distill.hip: a single workgroup of four waves, one wave per row, reductions by wave
 // shuffles, the per-wave partial sums through LDS and added in index order -- no atomics, a fixed order of summation, two runs give the
 // same bits.  The loss is element-wise, so a row is read exactly once either way; a row of up to ROW_REG * 64 columns has all its loads
 // issued before the arithmetic and sits in registers (lane l holds columns l, l + 64, ...), a longer row takes a strided loop.

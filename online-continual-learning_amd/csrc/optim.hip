@@ -1,11 +1,56 @@
-// K8b: torch.optim.Adam over the flat parameter array as one kernel.  HBM-bound fp32 streaming like sgd_flat (small_ops.hip): four
+// K8 / K8b: the two optimisers over the flat parameter array, one flat_dev.h kernel each.
+// K8: torch.optim.SGD (weight decay, no momentum): 16-byte loads of p and g, one store, 12 bytes per element.
+// K8b: torch.optim.Adam over the flat parameter array as one kernel.  HBM-bound fp32 streaming like sgd_flat: four
 // 16-byte loads (p, g, m, v) and three stores (p, m, v) per four elements, 28 bytes per element; no LDS, no atomics, no reduction.
 // IEEE sqrtf and '/' (the compiler's default): nothing in this file may be built with fast-math or replaced by an approximation.
 #include "flat_dev.h"
+#include "small_ops.h"
 #include <math.h>
 
 using namespace ocl;
 
+// =====================================================================================================
+// K8 SGD (flat)
+// =====================================================================================================
+namespace ocl {
+SPlan plan_sgd(const void* params, const void* grads, const void* out, int64_t n) {
+    if (!aligned16(params, grads, out)) return splan(OCL_PATH_SGD_REFUSED);
+    const int blocks = (int)min((int64_t)2048, (n / 4 + 255) / 256 + 1);
+    const bool more_trips = n / 4 > (int64_t)blocks * 256;
+    return splan(more_trips ? OCL_PATH_SGD_GRID_CAP : (n % 4) ? OCL_PATH_SGD_TAIL : OCL_PATH_SGD_VEC, (unsigned)blocks, 1, 256);
+}
+}  // namespace ocl
+
+__global__ void __launch_bounds__(256) sgd_flat(float* __restrict__ p, const float* __restrict__ g, int64_t n, float lr,
+                                                float wd, float gs, float* __restrict__ out) {
+    float* o = out ? out : p;
+    flat_for_each(n, [&](auto at) {
+        auto a = at.load(p);
+        const auto b = at.load(g);
+#pragma unroll
+        for (int k = 0; k < at.W; ++k) a[k] = fmaf(-lr, fmaf(wd, a[k], b[k] * gs), a[k]);
+        at.store(o, a);
+    });
+}
+
+int ocl_sgd_step(float* params, const float* grads, int64_t n, float lr, float weight_decay, float grad_scale, float* out,
+                 void* stream) {
+    OCL_REQUIRE(params && grads && n > 0, "sgd: null pointer or n<=0");
+    // a backward whose one-pass BatchNorm timed out has poisoned `grads` with NaN: refuse the step instead of applying it (the word
+    // is read without synchronising; a time-out that lands after this check is caught by the next forward, before its step)
+    if (int arc = ocl::check_async_error("sgd_step")) return arc;
+    const SPlan pl = plan_sgd(params, grads, out, n);
+    OCL_REQUIRE(pl.path != OCL_PATH_SGD_REFUSED, "sgd: pointers must be 16-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(PROF_BN, s);
+    hipLaunchKernelGGL(sgd_flat, dim3(pl.grid_x), dim3(pl.block), 0, s, params, grads, n, lr, weight_decay, grad_scale, out);
+    OCL_LAUNCH_CHECK();
+    return OCL_OK;
+}
+
+// =====================================================================================================
+// K8b Adam (flat)
+// =====================================================================================================
 // the constants of one step, formed in double on the host (ocl_adam_step) and passed by value
 struct AdamStep {
     float omb1, beta2, omb2;   // 1 - beta1, beta2, 1 - beta2

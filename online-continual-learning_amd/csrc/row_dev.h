@@ -1,4 +1,4 @@
-// The one row skeleton of the per-row loss kernels (K6 cross-entropy, segmented cross-entropy and distillation, K12 MIR in small_ops.hip;
+// The one row skeleton of the per-row loss kernels (K6 cross-entropy, segmented cross-entropy and distillation, K12 MIR in row_losses.hip;
 // K6b ce_kd_blend in distill.hip; K6c bce_distill in icarl.hip; K6d row_argmax_groupsum in rowstats.hip; K6e der_loss in der.hip): one
 // wave per row, lane l owning columns l, l + 64, ..., and the two row formulas that more than one of them evaluates.
 //
@@ -20,7 +20,7 @@
 // hand and reads nothing), the rounding barriers of ce_kd_blend's and bce_distill's gradients (they stay at their sites), the register
 // form for ce_kernel, ce_seg_kernel, kd_kernel and mir_kernel (strided today; moving them would be a speed change), the grids of
 // mir_kernel and row_argmax_groupsum_kernel (four rows per workgroup and no cross-row sum: ROW_WAVES alone), supcon_rows, the NCM
-// kernels and the cosine kernels' (r0 + r1) + (r2 + r3) block stage (small_ops.hip), and the head chain of net.hip.
+// kernels and the cosine kernels' (r0 + r1) + (r2 + r3) block stage (supcon.hip, ncm.hip, cosine.hip), and the head chain of net.hip.
 // Sent back to their own statements for speed (same bits on the header, but a mean kernel time above the parent's by more than the
 // parent's own run-to-run difference of 0.00 - 0.02 us, at n = 10 and 20 rows of c = 100; profiles/row_family_kernel_times.txt):
 //   * ce_seg_kernel: its own row (ce_row_seg), loop and fold.  On ce_row with a column predicate, ROW_FOR_EACH and row_fold: 9.16 - 9.27 us

@@ -89,7 +89,7 @@ def near_tie_ulps(c, ef, cf):
 
 
 def path_k(path, dim):
-    """float32 roundings on the longest way from the features to a key of knn_sv_kernel (csrc/small_ops.hip), so that
+    """float32 roundings on the longest way from the features to a key of knn_sv_kernel (csrc/aser.hip), so that
     |key - d| <= ((1 + 2^-24)^K - 1) d <= 1.01 K 2^-24 d for a distance d (every term is >= 0: sum |terms| = d):
       * t = e - v is rounded once, and t * t carries that factor twice: 2;
       * s = fmaf(t, t, s) rounds once per step, and the first term of a chain passes through every step of it.  KNN_VEC_*: lane q of four

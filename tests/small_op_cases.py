@@ -1,5 +1,5 @@
-"""The parity cases of the small kernels (csrc/small_ops.hip: gather / scatter, SGD, cosine-max, cross-entropy and its relatives, SupCon,
-kNN-Shapley, column reductions, argsort, NCM, the small MFMA GEMM, the SCR augmentation), shared by tests/test_cpu_small_ops.py (every kernel and every path
+"""The parity cases of the small kernels (one file of csrc/ per family, SOURCES below: gather / scatter, SGD, cosine-max, cross-entropy and its
+relatives, SupCon, kNN-Shapley, column reductions, argsort, NCM, the small MFMA GEMM, the SCR augmentation), shared by tests/test_cpu_small_ops.py (every kernel and every path
 code of ocl_test_small_op_path is claimed by a case that still reaches it; no GPU) and tests/test_gpu_small_ops.py (runs every case).
 
 Plain data.  A case is a dict:
@@ -13,7 +13,17 @@ Plain data.  A case is a dict:
 
 ALIGNED = 1 << 20          # a 16-byte aligned stand-in address for the CPU test (the export looks at alignment only)
 
-# op name -> (op code of include/ocl_hip.h, the __global__ kernels of small_ops.hip its cases run)
+# the files of csrc/ that hold the kernels of OPS, each family's launch plan, kernels and entry points side by side
+SOURCES = ["buffer_rows.hip", "loader.hip", "optim.hip", "cosine.hip", "row_losses.hip", "supcon.hip", "aser.hip", "ncm.hip", "augment.hip",
+           "gemm_small.hip"]
+# the other __global__ kernels of those files -> the test module whose cases run them
+OTHER_SUITES = {
+    "adam_flat_kernel": "test_gpu_adam.py",
+    "gather_f32_hwc_f32_chw_kernel": "test_gpu_datasets.py",
+    "gather_f32_hwc_f32_chw_scalar_kernel": "test_gpu_datasets.py",
+}
+
+# op name -> (op code of include/ocl_hip.h, the __global__ kernels of SOURCES its cases run)
 OPS = {
     "rows": (0, ["rows_copy16", "rows_copy4"]),
     "pair": (1, ["rows_gather_pair"]),

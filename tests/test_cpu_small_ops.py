@@ -1,7 +1,8 @@
-"""CPU: the parity suite of the small kernels (tests/test_gpu_small_ops.py) covers what csrc/small_ops.hip can do.
+"""CPU: the parity suite of the small kernels (tests/test_gpu_small_ops.py) covers what the small-op files of csrc/ can do (small_op_cases.SOURCES:
+one file per kernel family, its launch plan, kernels and entry points side by side).
 
-* every __global__ kernel of the file and every path code ocl_test_small_op_path can return (the very functions the entry points launch
-  from) is claimed by a case of tests/small_op_cases.py, and every case still reaches the path it claims;
+* every __global__ kernel of those files (each defined in one of them; the few that belong to another suite are named, with that suite)
+  and every path code ocl_test_small_op_path can return (the very functions the entry points launch from) is claimed by a case of tests/small_op_cases.py, and every case still reaches the path it claims;
 * the GPU file parametrizes every case of the table, unsliced;
 * the float64 reference functions of the GPU file reproduce the reference project's own fp32 results stored in tests/golden/ (so the
   references the kernels are judged against are themselves pinned);
@@ -43,9 +44,21 @@ def path_of(lib, op, case, ptrs=None):
     return code, plan
 
 
+def sources():
+    """file name -> text, of every file of SC.SOURCES."""
+    return {f: open(os.path.join(ROOT, "online-continual-learning_amd", "csrc", f)).read() for f in SC.SOURCES}
+
+
 def test_every_kernel_of_the_file_is_claimed():
-    src = open(os.path.join(ROOT, "online-continual-learning_amd", "csrc", "small_ops.hip")).read()
-    kernels = set(re.findall(r"__global__\s+void\s+(?:__launch_bounds__\(\d+\)\s+)?(\w+)\s*\(", src))
+    found = [(k, f) for f, src in sources().items()
+             for k in re.findall(r"__global__\s+void\s+(?:__launch_bounds__\(\w+\)\s+)?(\w+)\s*\(", src)]
+    # a kernel of these files belongs to the table or, by name, to another suite that exists: nothing is let off by the file it is in
+    assert set(SC.OTHER_SUITES) <= {k for k, _ in found}, sorted(SC.OTHER_SUITES)
+    for module in SC.OTHER_SUITES.values():
+        assert os.path.exists(os.path.join(ROOT, "tests", module)), module
+    table = [(k, f) for k, f in found if k not in SC.OTHER_SUITES]
+    kernels = {k for k, _ in table}
+    assert len(table) == len(kernels), "a kernel is defined in two files: %s" % sorted(table)
     assert len(kernels) == 22, sorted(kernels)
     claimed = {k for op, (_, ks) in SC.OPS.items() if SC.CASES[op] for k in ks}
     assert kernels - claimed == set(SC.EXEMPT_KERNELS), sorted(kernels - claimed)
@@ -58,8 +71,7 @@ def test_every_path_code_is_claimed_and_every_case_reaches_its_path(lib):
     assert len(paths) >= 45 and len(set(paths.values())) == len(paths)
     # the plan functions return these constants only (the size / form variants of the cosine and SupCon paths by offset from the first,
     # pinned by static_asserts there): a new branch needs a new constant here, and a constant needs a case below
-    src = open(os.path.join(ROOT, "online-continual-learning_amd", "csrc", "small_ops.hip")).read()
-    used = set(re.findall(PFX + r"([A-Z0-9_]+)", src))
+    used = {name for src in sources().values() for name in re.findall(PFX + r"([A-Z0-9_]+)", src)}
     assert used <= set(paths) and set(paths) - used <= {n for n in paths if n.startswith(("COS_", "SUPCON_"))}, sorted(set(paths) ^ used)
     claimed = set()
     for op, cases in SC.CASES.items():

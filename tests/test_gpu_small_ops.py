@@ -1,4 +1,4 @@
-"""GPU: every kernel of csrc/small_ops.hip, the two augmentation kernels included, path by path (tests/small_op_cases.py), against float64 references
+"""GPU: every kernel of the small-op files of csrc/ (small_op_cases.SOURCES), the two augmentation kernels included, path by path (tests/small_op_cases.py), against float64 references
 written here (the augmentation's: tests/augment_ref.py) from the formulas include/ocl_hip.h cites -- independent of oracle/ (fp32) and of the library.
 
 Tier 1 (bit-equal, data chosen so that fp32 is exact): gather / scatter / pair / u8 (any data), the small GEMM and the column reductions on small
